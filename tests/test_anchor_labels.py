@@ -1,5 +1,5 @@
 """RetinaNet anchor labelling (row f4): oracle pinning on the CPU, HIP parity on the GPU."""
-import importlib.util
+import hashlib
 import os
 
 import numpy as np
@@ -8,7 +8,6 @@ import pytest
 from oracle import anchors as OA
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_SO = os.path.join(os.path.dirname(HERE), "oracle", "_pyref", "cython_bbox.so")
 
 
 def rand_gts(rng, n, H=640, W=896, integer=False):
@@ -41,17 +40,17 @@ def test_cell_anchors_known_answers_and_product_module():
     assert anchors.shape == (9 * (128 ** 2 + 64 ** 2 + 32 ** 2 + 16 ** 2 + 8 ** 2), 4)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_pyref/cython_bbox.so not built "
-                    "(make -C oracle pyref, needs /root/reference)")
-def test_oracle_iou_bit_exact_vs_compiled_reference():
-    spec = importlib.util.spec_from_file_location("cython_bbox", REF_SO)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+def test_oracle_iou_bit_exact_vs_compiled_reference(golden_dir):
+    """tests/golden/iou_ref.npz (tests/golden/make_iou_golden.py): the SHA-256 of what the reference's compiled
+    IoU routine returned for every anchor against 37 random and 37 integer (tie-producing) ground-truth boxes;
+    the oracle's output must have the same bytes."""
+    z = np.load(os.path.join(golden_dir, "iou_ref.npz"))
     anchors, _ = OA.all_anchors()
-    rng = np.random.default_rng(5)
-    for integer in (False, True):
-        g, _ = rand_gts(rng, 37, integer=integer)
-        assert np.array_equal(ref.bbox_overlaps(anchors, g), OA.bbox_overlaps(anchors, g))
+    for case in ("random", "integer"):
+        got = OA.bbox_overlaps(anchors, z["gts_" + case])
+        assert got.dtype == np.float32 and got.shape == tuple(z["shape_" + case]), case
+        digest = hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest()
+        assert digest == str(z["sha256_" + case]), case
 
 
 def test_oracle_labelling_invariants():

@@ -75,7 +75,7 @@ def test_scale_readiness_forced_one_rank_communicator():
     """the line a SCALE run produces, exercised on one GPU with the collectives forced onto a
     one-rank RCCL communicator (SSAD_DP_FORCE=1): n_gpus / parallelism present, bucket all-reduces really issued
     inside the timed steps (subnets: 2 buckets, backbone: 4), and a step that issues them costs what a step that
-    does not costs (the GPU_MAX_HW_QUEUES=7 setting of bench.py) -- within 2 % here (1 % is the
+    does not costs (the hardware-queue setting of bench.py) -- within 2 % here (1 % is the
     in-call repeat spread of the step itself)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")

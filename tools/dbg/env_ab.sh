@@ -6,8 +6,6 @@ run "X=1"
 run "ROC_SIGNAL_POOL_SIZE=4096"
 run "ROC_AQL_QUEUE_SIZE=65536"
 run "HIP_FORCE_DEV_KERNARG=0"
-run "GPU_MAX_HW_QUEUES=8"
-run "GPU_MAX_HW_QUEUES=4"
 run "ROC_CPU_WAIT_FOR_SIGNAL=0"
 run "SSAD_TEACHER_FIRST=0"
 run "X=2"
