@@ -455,6 +455,46 @@ SSAD_API int ssad_retinanet_anchor_labels(
     ssad_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Input blobs from uint8 images on the device                             */
+/* ---------------------------------------------------------------------- */
+
+/* Replaces the host-side image half of the minibatch (detectron/lib/roi_data/minibatch.py:102-134 +
+ * detectron/lib/utils/blob.py:40-106: preprocess_im, cv2.resize INTER_LINEAR with fx = fy = im_scale,
+ * im_list_to_blob), which the reference runs per image and once per network: one call writes `data` and
+ * `teacher/data` (n_norms = 2, norms_host[0] the student's) or one blob (n_norms = 1) from ONE upload of the
+ * decoded pixels.
+ *   src              device, the images packed back to back as uint8 [h][w][3] (HWC, BGR: what cv2.imread
+ *                    returns); image n starts at byte offset_host[n]
+ *   h/w_host         source size, out_h/out_w_host the resized size (rint(h s), rint(w s), half to even),
+ *                    scale_host the image's scale s (double), flipped_host != 0: source column col is read
+ *                    at w - 1 - col (im[:, ::-1, :] before everything else)
+ *   norms_host[k]    blob k: t = ((float)u8 / div - mean[c]) / std[c] in float, true divisions; out: device
+ *                    float [N][3][Hb][Wb], 16-byte aligned, written completely (zero padding included: no
+ *                    memset needed)
+ * Element (n, c, y, x) is +0.0f for y >= out_h or x >= out_w, else the 2 x 2 bilinear interpolation, no
+ * antialiasing, of the normalised taps at fx = (float)((x + 0.5) * (1.0 / s) - 0.5) (double arithmetic),
+ * sx = floor(fx), ax = fx - sx, (sx, ax) = (0, 0) below 0 and (w - 1, 0) from w - 1 on; rows alike.
+ * SSAD_E_BADARG, before any launch, for: a null pointer, N < 1 or N > SSAD_IMAGE_BLOBS_MAX_BATCH (the
+ * per-image sizes travel as a kernel argument), n_norms not 1 or 2, Wb % 4 != 0 (16-byte stores), h or w < 1,
+ * out_h / out_w < 1 or beyond Hb / Wb, offset < 0 or offset + 3 h w > src_bytes, a scale that is not finite
+ * and > 0, div or a std that is 0 or not finite, a mean that is not finite, a blob of 2^31 elements or more, an out
+ * or a workspace that is not 16-byte aligned.
+ * SSAD_E_WORKSPACE for a workspace below ssad_image_blobs_workspace_bytes (0 = unsupported shape).
+ * Two launches on `stream`: a tiny one fills the workspace (tap value table, per-image row / column entries),
+ * the second writes the blobs.  Do not share a workspace between streams. */
+#define SSAD_IMAGE_BLOBS_MAX_BATCH 64
+typedef struct ssad_image_norm {
+  float div, mean[3], std[3];
+  float* out;          /* device [N][3][Hb][Wb] */
+} ssad_image_norm;
+SSAD_API size_t ssad_image_blobs_workspace_bytes(int N, int Hb, int Wb);
+SSAD_API int ssad_image_blobs(
+    const unsigned char* src, size_t src_bytes, const long long* offset_host, const int* h_host,
+    const int* w_host, const int* out_h_host, const int* out_w_host, const double* scale_host,
+    const int* flipped_host, int N, int Hb, int Wb, const ssad_image_norm* norms_host, int n_norms,
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Default convolution engine helpers and MaxPool (backbone, row f1)        */
 /* ---------------------------------------------------------------------- */
 

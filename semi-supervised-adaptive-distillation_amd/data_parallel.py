@@ -19,8 +19,17 @@ Backend-agnostic: the same code runs under "gloo" on CPU tensors (tests).
 import torch
 
 
+def _blocking_collectives_use_current_stream():
+    """torch's NCCL / RCCL process group runs a collective issued with async_op=False on the caller's current
+    stream since the release that gave the collective options their `asyncOp` field; before that every
+    collective ran on the group's internal stream."""
+    import torch.distributed as dist
+    return hasattr(dist.AllreduceOptions(), "asyncOp")
+
+
 class BucketedAllReduce(object):
     issued_total = 0        # collectives started by every instance of this process (bench.py reports the rate)
+    _comm = {}              # device -> the communication stream every instance of this process shares
 
     def __init__(self, process_group=None, world_size=1):
         self.pg = process_group
@@ -39,17 +48,45 @@ class BucketedAllReduce(object):
         if not self.active:
             return
         import torch.distributed as dist
-        # On GPU the collective runs on RCCL's own stream; torch orders it after
-        # the kernels already enqueued on the current stream (the HIP kernels
-        # of this package launch on torch's current stream) and work.wait()
-        # orders later kernels after it.
-        self._pending.append(dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.pg,
-                                             async_op=True))
         BucketedAllReduce.issued_total += 1
+        if not bucket.is_cuda or not _blocking_collectives_use_current_stream():
+            # CPU (gloo) buckets, and GPU buckets under a torch whose process group runs every collective on its
+            # internal stream: the asynchronous work handle, waited for in wait()
+            self._pending.append(dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
+            return
+        # On the GPU the collective runs on a HIGH-PRIORITY stream of this class's own, ordered after the
+        # kernels already enqueued on the current stream (the HIP kernels of this package launch on torch's
+        # current stream); wait() orders later kernels after it.  The process group's internal stream is a
+        # normal-priority one and lands on one of the few hardware queues the teacher's and the filter
+        # gradients' streams are mapped onto: whatever shares its queue then sits behind the collective's
+        # wait for the step's stream instead of running beside it (profiles/r04_hw_queues.md: +2.6 ms per
+        # step at 4 queues).  The high-priority queues hold nothing but the step's own stream and this one.
+        # Needs a torch whose process group enqueues a BLOCKING collective on the current stream (the releases
+        # that have AllreduceOptions.asyncOp; developed on 2.10): the current stream is the communication
+        # stream here.  The ordering below is correct either way -- on a torch that still used its internal
+        # stream the blocking call would make the communication stream wait for it -- only the placement on
+        # the hardware queues depends on it.
+        cur = torch.cuda.current_stream(bucket.device)
+        comm = self._comm_stream(bucket.device)
+        comm.wait_stream(cur)
+        with torch.cuda.stream(comm):
+            dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.pg, async_op=False)
+        done = torch.cuda.Event()
+        done.record(comm)
+        self._pending.append(done)
+
+    def _comm_stream(self, device):
+        s = self._comm.get(device)
+        if s is None:
+            s = BucketedAllReduce._comm[device] = torch.cuda.Stream(device=device, priority=-1)
+        return s
 
     def wait(self):
         for w in self._pending:
-            w.wait()
+            if isinstance(w, torch.cuda.Event):
+                torch.cuda.current_stream().wait_event(w)
+            else:
+                w.wait()
         self._pending = []
 
     def broadcast(self, tensors, src=0):

@@ -96,6 +96,14 @@ class F16WgradLevel(C.Structure):
     _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int)]
 
 
+IMAGE_BLOBS_MAX_BATCH = 64     # SSAD_IMAGE_BLOBS_MAX_BATCH
+
+
+class ImageNorm(C.Structure):
+    """ssad_image_norm (include/ssad_kernels.h): one output blob of ssad_image_blobs and its normalisation."""
+    _fields_ = [("div", C.c_float), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("out", C.c_void_p)]
+
+
 class F16Level(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("aux", C.c_void_p),
                 ("N", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -254,6 +262,10 @@ def lib():
     L.ssad_grouped_conv3x3_f16_filter_halves.argtypes = [i32, i32]
     L.ssad_grouped_conv3x3_f16_pack_filter.argtypes = [vp, i32, i32, vp, vp]
     L.ssad_grouped_conv3x3_f16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.ssad_image_blobs_workspace_bytes.restype = sz
+    L.ssad_image_blobs_workspace_bytes.argtypes = [i32, i32, i32]
+    L.ssad_image_blobs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(ImageNorm), i32,
+                                   vp, sz, vp]
     L.ssad_kernels_arch.restype = C.c_char_p
     L.ssad_kernels_abi_version.restype = i32
     if L.ssad_kernels_abi_version() != ABI_VERSION:
