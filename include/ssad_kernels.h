@@ -707,6 +707,82 @@ SSAD_API int ssad_retinanet_detect(
     float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
     int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream);
 
+/* Soft-NMS (detectron/lib/utils/cython_nms.pyx:98-203 behind utils/boxes.py:321-338) on class-sorted
+ * candidates, the arrays ssad_retinanet_detect builds: boxes [n][4], scores [n], cls [n] ascending with -1 in
+ * the empty trailing slots.  One workgroup per class walks its segment; while candidates remain it
+ *   1. picks the live candidate with the highest CURRENT score (equal scores: the lower position first -- the
+ *      reference's order among equal scores depends on its swap history and is unspecified);
+ *   2. records pick rank and current score, retires it;
+ *   3. for every other live candidate j, float32, every operation rounded on its own:
+ *      iw = min(x2) - max(x1) + 1, ih = min(y2) - max(y1) + 1, ov = iw*ih / (area_i + area_j - iw*ih);
+ *   4. ONLY IF iw > 0 and ih > 0: score_j *= weight, then j is retired if score_j < score_thresh
+ *      (a candidate that never overlaps a pick is never tested and survives below the threshold: the reference's rule).
+ * weight:  SSAD_NMS_SOFT_HARD      ov > Nt ? 0 : 1      (NOT the greedy kernel, which removes at ovr >= thresh
+ *                                                        through its bit-matrix and never looks at score_thresh)
+ *          SSAD_NMS_SOFT_LINEAR    ov > Nt ? 1 - ov : 1
+ *          SSAD_NMS_SOFT_GAUSSIAN  exp(-ov*ov / sigma)
+ * Without equal current scores at a pick this is the reference's function bit for bit (hard, linear; gaussian up
+ * to the exp).  Segments of at most SSAD_SOFT_NMS_LDS_CAP candidates work in LDS (20 bytes each), longer ones on
+ * the workspace.  The walk is serial in the number of picks.
+ *   keys_out[i]       (decayed score bits << 32) | ~i for a pick, 0 for a retired candidate or an empty slot:
+ *                     the word the greedy scan writes, so the rank sort and the emit kernel serve both
+ *   pick_rank_out[i]  rank of the pick within its class, -1 when retired / empty
+ * SSAD_NMS_GREEDY is not a method of this entry (SSAD_E_BADARG), nor is sigma <= 0 or n < 0; n == 0 launches nothing. */
+#define SSAD_NMS_GREEDY 0
+#define SSAD_NMS_SOFT_HARD 1
+#define SSAD_NMS_SOFT_LINEAR 2
+#define SSAD_NMS_SOFT_GAUSSIAN 3
+#define SSAD_SOFT_NMS_LDS_CAP 1024
+SSAD_API size_t ssad_soft_nms_workspace_bytes(int n);
+SSAD_API int ssad_soft_nms(const float* boxes, const float* scores, const int* cls, int n, int C, int method,
+                           float sigma, float Nt, float score_thresh, unsigned long long* keys_out,
+                           int* pick_rank_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream);
+/* Bounding-box voting (utils/boxes.py:262-311; IoU as utils/cython_bbox.pyx:32-72, float32).  One wave per top
+ * detection k < m with keys_inout[k] != 0 and top_cls[k] >= 0: the voters are the candidates of class top_cls[k]
+ * (boxes / scores / cls as above: ORIGINAL boxes and scores, test.py:791-797) with IoU(top_boxes[k], .) >= vote_thresh;
+ *   voted_boxes_out[k] = sum(score * box) / sum(score)   -- its own array: others keep voting with the originals
+ * and the score in the high half of keys_inout[k] becomes
+ *   SSAD_VOTE_ID unchanged | AVG mean(ws) | IOU_AVG sum(ws * iou) / sum(iou) | GENERALIZED_AVG mean(ws^beta)^(1/beta)
+ *   | QUASI_SUM sum(ws) / count^beta | TEMP_AVG mean(p^(1/beta) / (p^(1/beta) + q^(1/beta))), p = ws / max(ws, 1 - ws),
+ *   q = (1 - ws) / max(ws, 1 - ws)  (boxes.py:282-292 with the exp / log folded into one power).
+ * In the detector top_* are the candidate arrays themselves (m = n), so a box always votes for itself; a top box
+ * that finds no voter keeps its box and score (the reference divides by zero).  beta <= 0 is SSAD_E_BADARG where
+ * it is an exponent (TEMP_AVG, GENERALIZED_AVG, QUASI_SUM). */
+#define SSAD_VOTE_ID 0
+#define SSAD_VOTE_TEMP_AVG 1
+#define SSAD_VOTE_AVG 2
+#define SSAD_VOTE_IOU_AVG 3
+#define SSAD_VOTE_GENERALIZED_AVG 4
+#define SSAD_VOTE_QUASI_SUM 5
+SSAD_API int ssad_box_voting(const float* top_boxes, const int* top_cls, int m, const float* boxes,
+                             const float* scores, const int* cls, int n, int C, float vote_thresh,
+                             int scoring_method, float beta, unsigned long long* keys_inout,
+                             float* voted_boxes_out, ssad_stream_t stream);
+/* ssad_retinanet_detect with the reference's two post-processing options (detectron/lib/core/test.py:779-797,
+ * TEST.SOFT_NMS / TEST.BBOX_VOTE).  post == NULL, or nms_method SSAD_NMS_GREEDY with vote == 0, IS
+ * ssad_retinanet_detect: the same launches.  Otherwise Soft-NMS (overlap threshold = nms_thresh, test.py:783)
+ * replaces the bit-matrix and the scan, and voting refines every survivor before the final sort by score
+ * (test_retinanet.py:191-194), so dets_per_im cuts on the final scores. */
+typedef struct {
+  int nms_method;        /* SSAD_NMS_* */
+  float sigma;           /* gaussian; > 0 for every soft method */
+  float score_thresh;    /* Soft-NMS retirement threshold (test.py:784 passes 0.0001) */
+  int vote;              /* 0 / 1 */
+  float vote_thresh;
+  int scoring_method;    /* SSAD_VOTE_* */
+  float beta;
+} ssad_detect_post;
+SSAD_API size_t ssad_retinanet_detect_ex_workspace_bytes(
+    int levels, int A, int C, const int* H_host, const int* W_host, int pre_nms_topn,
+    const ssad_detect_post* post);
+SSAD_API int ssad_retinanet_detect_ex(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
+    float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
+    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
+    const ssad_detect_post* post);
+
 /* ---------------------------------------------------------------------- */
 /* fp16 storage / fp32 accumulation (BASELINE config 5's precision)        */
 /* ---------------------------------------------------------------------- */

@@ -17,6 +17,8 @@
 //   4. 64 x 64 suppression bit-matrix for same-class pairs, then one workgroup per
 //      class walks its segment in score order (the serial part of greedy NMS);
 //   5. order the survivors by score (rank sort), emit the first dets_per_im.
+// ssad_retinanet_detect_ex (core/test.py:779-797) may replace step 4 by Soft-NMS and add bounding-box voting before
+// step 5: both are soft_nms.hip's and write the same survivor words.
 // Score ties are broken by element index (the reference's argpartition / argsort
 // leave them unspecified).  Every kernel is this file's: rounds 1-5 sorted with rocPRIM's radix sort through
 // hipCUB (the whole 8.6 M-key array of an image for the top 1000 per level); the rank sort is O(n^2) comparisons
@@ -388,21 +390,51 @@ size_t ssad_retinanet_detect_workspace_bytes(int levels, int A, int C, const int
          2 * al(n * 8);
 }
 
-int ssad_retinanet_detect(
+}  // extern "C"
+
+namespace {
+
+// what the post-processing options add behind the greedy path's workspace: pick ranks, Soft-NMS's own workspace,
+// the voted boxes
+size_t post_bytes(size_t n) { return al(n * 4) + al(ssad_soft_nms_workspace_bytes((int)n)) + al(n * 16); }
+
+bool post_is_plain(const ssad_detect_post* post) {
+  return !post || (post->nms_method == SSAD_NMS_GREEDY && !post->vote);
+}
+
+int check_post(const ssad_detect_post* post) {
+  if (!post) return 0;
+  if (post->nms_method < SSAD_NMS_GREEDY || post->nms_method > SSAD_NMS_SOFT_GAUSSIAN) return SSAD_E_BADARG;
+  if (post->nms_method != SSAD_NMS_GREEDY && !(post->sigma > 0.0f)) return SSAD_E_BADARG;
+  if (post->vote) {
+    const int m = post->scoring_method;
+    if (m < SSAD_VOTE_ID || m > SSAD_VOTE_QUASI_SUM) return SSAD_E_BADARG;
+    if ((m == SSAD_VOTE_TEMP_AVG || m == SSAD_VOTE_GENERALIZED_AVG || m == SSAD_VOTE_QUASI_SUM) &&
+        !(post->beta > 0.0f))
+      return SSAD_E_BADARG;
+  }
+  return 0;
+}
+
+// the body of ssad_retinanet_detect and ssad_retinanet_detect_ex; post == nullptr (or greedy without voting) makes
+// the launches ssad_retinanet_detect has always made
+int detect_body(
     const float* const* cls_prob_host, const float* const* box_pred_host,
     const double* cell_anchors, int levels, int A, int C, int k_min, const int* H_host,
     const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
     float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
-    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream) {
+    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
+    const ssad_detect_post* post) {
   Plan pl;
   DArgs a;
   const int rc = make_plan(levels, A, C, H_host, W_host, pre_nms_topn, &pl, a.estart);
   if (rc) return rc;
   if (!cls_prob_host || !box_pred_host || !cell_anchors || !dets_out || !count_out ||
-      dets_per_im < 1 || dets_per_im > pl.n || !(im_scale > 0.0f))
+      dets_per_im < 1 || dets_per_im > pl.n || !(im_scale > 0.0f) || check_post(post))
     return SSAD_E_BADARG;
-  const size_t need = ssad_retinanet_detect_workspace_bytes(levels, A, C, H_host, W_host,
-                                                            pre_nms_topn);
+  if (post_is_plain(post)) post = nullptr;
+  const size_t need = ssad_retinanet_detect_ex_workspace_bytes(levels, A, C, H_host, W_host,
+                                                               pre_nms_topn, post);
   if (!workspace || workspace_bytes < need) return SSAD_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   for (int l = 0; l < SSAD_MAX_LEVELS; ++l) {
@@ -437,6 +469,14 @@ int ssad_retinanet_detect(
   unsigned long long* mask = (unsigned long long*)take(n * (size_t)pl.words * 8);
   unsigned long long* fkeys = (unsigned long long*)take(n * 8);
   unsigned long long* fkeys_s = (unsigned long long*)take(n * 8);
+  int* pick_rank = nullptr;
+  void* soft_ws = nullptr;
+  float* voted = nullptr;
+  if (post) {
+    pick_rank = (int*)take(n * 4);
+    soft_ws = take(ssad_soft_nms_workspace_bytes(pl.n));
+    voted = (float*)take(n * 16);
+  }
 
   if (pl.total > 0) {
     long long blocks = (pl.total + kT - 1) / kT;
@@ -468,16 +508,67 @@ int ssad_retinanet_detect(
   hipLaunchKernelGGL(det_rank_sort_kernel, dim3((unsigned)nb, 1), dim3(kT), 0, s, ckeys, cvals, pl.n, 0, ckeys_s, cvals_s);
   hipLaunchKernelGGL(det_gather_kernel, dim3(nb), dim3(kT), 0, s, pl.n, ckeys_s, cvals_s, boxes,
                      scores, sboxes, sscores, scls);
-  hipLaunchKernelGGL(det_nms_mask_kernel, dim3(pl.words, pl.words), dim3(64), 0, s, pl.n, pl.words,
-                     sboxes, scls, nms_thresh, mask);
-  (void)hipMemsetAsync(fkeys, 0, n * 8, s);
-  hipLaunchKernelGGL(det_nms_scan_kernel, dim3(C), dim3(kT), (size_t)pl.words * 8, s, pl.n, pl.words,
-                     C, scls, sscores, mask, fkeys);
+  if (!post || post->nms_method == SSAD_NMS_GREEDY) {
+    // greedy: suppression at ovr >= nms_thresh, decided ahead in the bit-matrix
+    hipLaunchKernelGGL(det_nms_mask_kernel, dim3(pl.words, pl.words), dim3(64), 0, s, pl.n, pl.words,
+                       sboxes, scls, nms_thresh, mask);
+    (void)hipMemsetAsync(fkeys, 0, n * 8, s);
+    hipLaunchKernelGGL(det_nms_scan_kernel, dim3(C), dim3(kT), (size_t)pl.words * 8, s, pl.n, pl.words,
+                       C, scls, sscores, mask, fkeys);
+  } else {
+    // Soft-NMS (its "hard" decays to 0 at ov > nms_thresh and retires below score_thresh): the same fkeys words
+    const int rs = ssad_soft_nms(sboxes, sscores, scls, pl.n, C, post->nms_method, post->sigma, nms_thresh,
+                                 post->score_thresh, fkeys, pick_rank, soft_ws,
+                                 ssad_soft_nms_workspace_bytes(pl.n), stream);
+    if (rs) return rs;
+  }
+  const float* out_boxes = sboxes;
+  if (post && post->vote) {
+    // every survivor votes before the final sort: a scoring method may change the order and the cut
+    const int rv = ssad_box_voting(sboxes, scls, pl.n, sboxes, sscores, scls, pl.n, C, post->vote_thresh,
+                                   post->scoring_method, post->beta, fkeys, voted, stream);
+    if (rv) return rv;
+    out_boxes = voted;
+  }
   hipLaunchKernelGGL(det_rank_sort_kernel, dim3((unsigned)nb, 1), dim3(kT), 0, s, fkeys, (const int*)nullptr, pl.n, 1, fkeys_s,
                      (int*)nullptr);
   hipLaunchKernelGGL(det_emit_kernel, dim3((dets_per_im + kT - 1) / kT), dim3(kT), 0, s, pl.n,
-                     dets_per_im, fkeys_s, sboxes, scls, dets_out, count_out);
+                     dets_per_im, fkeys_s, out_boxes, scls, dets_out, count_out);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ssad_retinanet_detect_ex_workspace_bytes(int levels, int A, int C, const int* H_host, const int* W_host,
+                                                int pre_nms_topn, const ssad_detect_post* post) {
+  const size_t base = ssad_retinanet_detect_workspace_bytes(levels, A, C, H_host, W_host, pre_nms_topn);
+  if (base == 0 || check_post(post)) return 0;
+  return post_is_plain(post) ? base : base + post_bytes((size_t)levels * pre_nms_topn);
+}
+
+int ssad_retinanet_detect(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
+    float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
+    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream) {
+  return detect_body(cls_prob_host, box_pred_host, cell_anchors, levels, A, C, k_min, H_host, W_host, inference_th,
+                     pre_nms_topn, nms_thresh, dets_per_im, im_scale, im_height, im_width, bbox_xform_clip, dets_out,
+                     count_out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int ssad_retinanet_detect_ex(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
+    float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
+    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
+    const ssad_detect_post* post) {
+  return detect_body(cls_prob_host, box_pred_host, cell_anchors, levels, A, C, k_min, H_host, W_host, inference_th,
+                     pre_nms_topn, nms_thresh, dets_per_im, im_scale, im_height, im_width, bbox_xform_clip, dets_out,
+                     count_out, workspace, workspace_bytes, stream, post);
 }
 
 }  // extern "C"

@@ -104,6 +104,16 @@ class ImageNorm(C.Structure):
     _fields_ = [("div", C.c_float), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("out", C.c_void_p)]
 
 
+class DetectPost(C.Structure):
+    """ssad_detect_post (include/ssad_kernels.h): Soft-NMS / box voting options of ssad_retinanet_detect_ex."""
+    _fields_ = [("nms_method", C.c_int), ("sigma", C.c_float), ("score_thresh", C.c_float), ("vote", C.c_int),
+                ("vote_thresh", C.c_float), ("scoring_method", C.c_int), ("beta", C.c_float)]
+
+
+NMS_METHODS = {"greedy": 0, "hard": 1, "linear": 2, "gaussian": 3}           # SSAD_NMS_*
+VOTE_SCORING = {"ID": 0, "TEMP_AVG": 1, "AVG": 2, "IOU_AVG": 3, "GENERALIZED_AVG": 4, "QUASI_SUM": 5}   # SSAD_VOTE_*
+
+
 class F16Level(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("aux", C.c_void_p),
                 ("N", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -266,6 +276,12 @@ def lib():
     L.ssad_image_blobs_workspace_bytes.argtypes = [i32, i32, i32]
     L.ssad_image_blobs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(ImageNorm), i32,
                                    vp, sz, vp]
+    L.ssad_soft_nms_workspace_bytes.restype = sz
+    L.ssad_soft_nms_workspace_bytes.argtypes = [i32]
+    L.ssad_soft_nms.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, sz, vp]
+    L.ssad_box_voting.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, f32, vp, vp, vp]
+    L.ssad_retinanet_detect_ex_workspace_bytes.restype = sz
+    L.ssad_retinanet_detect_ex_workspace_bytes.argtypes = [i32, i32, i32, vp, vp, i32, C.POINTER(DetectPost)]
     L.ssad_kernels_arch.restype = C.c_char_p
     L.ssad_kernels_abi_version.restype = i32
     if L.ssad_kernels_abi_version() != ABI_VERSION:

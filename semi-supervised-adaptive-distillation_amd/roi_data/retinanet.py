@@ -83,10 +83,17 @@ class RetinanetDetector(object):
 
     `__call__(cls_probs, box_preds, im_height, im_width, im_scale)` takes the per-level
     sigmoid scores [1][A*C][H][W] and box deltas [1][A*4][H][W] (device tensors) and
-    returns float32 [n <= dets_per_im][6] = x1, y1, x2, y2, score, class."""
+    returns float32 [n <= dets_per_im][6] = x1, y1, x2, y2, score, class.
+
+    The reference's two post-processing options (core/test.py:779-797), both None by default:
+    `soft_nms` = dict(method='linear' | 'gaussian' | 'hard', sigma=0.5, score_thresh=0.0001) replaces the greedy NMS
+    by Soft-NMS (TEST.SOFT_NMS; the overlap threshold stays `nms_thresh`, test.py:783); `bbox_vote` =
+    dict(vote_th=0.8, scoring_method='ID', beta=1.0) refines every survivor by box voting (TEST.BBOX_VOTE).  The
+    output is sorted by the final scores and cut at dets_per_im as before."""
 
     def __init__(self, level_shapes, cfg=AnchorConfig, inference_th=0.05, pre_nms_topn=1000,
-                 nms_thresh=0.5, dets_per_im=100, device="cuda"):
+                 nms_thresh=0.5, dets_per_im=100, device="cuda", *, soft_nms=None, bbox_vote=None):
+        self.post = self._post(soft_nms, bbox_vote)
         self.cfg = cfg
         self.levels = len(level_shapes)
         self.A = cfg.scales_per_octave * len(cfg.aspect_ratios)
@@ -100,13 +107,49 @@ class RetinanetDetector(object):
         self.shapes = list(level_shapes)
         L = K.lib()
         L.ssad_retinanet_detect_workspace_bytes.restype = C.c_size_t
-        nb = L.ssad_retinanet_detect_workspace_bytes(self.levels, self.A, self.C, self._H, self._W,
-                                                     self.topn)
+        if self.post is None:
+            nb = L.ssad_retinanet_detect_workspace_bytes(self.levels, self.A, self.C, self._H, self._W,
+                                                         self.topn)
+        else:
+            nb = L.ssad_retinanet_detect_ex_workspace_bytes(self.levels, self.A, self.C, self._H, self._W,
+                                                            self.topn, C.byref(self.post))
         if nb == 0:
             raise K.KernelError("retinanet_detect: unsupported geometry")
         self.ws = torch.empty(int(nb), dtype=torch.uint8, device=device)
         self.out = torch.zeros((dets_per_im, 6), dtype=torch.float32, device=device)
         self.count = torch.zeros(1, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def _post(soft_nms, bbox_vote):
+        """The ssad_detect_post of the two option dicts, or None for the plain greedy path; checked before the
+        library is touched."""
+        if soft_nms is None and bbox_vote is None:
+            return None
+        post = K.DetectPost(nms_method=K.NMS_METHODS["greedy"], sigma=0.5, score_thresh=0.0001, vote=0,
+                            vote_thresh=0.8, scoring_method=K.VOTE_SCORING["ID"], beta=1.0)
+        if soft_nms is not None:
+            opts = dict(method="linear", sigma=0.5, score_thresh=0.0001)
+            if set(soft_nms) - set(opts):
+                raise K.KernelError("soft_nms options: %s" % ", ".join(sorted(opts)))
+            opts.update(soft_nms)
+            if opts["method"] not in ("hard", "linear", "gaussian"):
+                raise K.KernelError("unknown soft_nms method %r" % (opts["method"],))
+            if not opts["sigma"] > 0:
+                raise K.KernelError("soft_nms: sigma must be positive")
+            post.nms_method, post.sigma = K.NMS_METHODS[opts["method"]], opts["sigma"]
+            post.score_thresh = opts["score_thresh"]
+        if bbox_vote is not None:
+            opts = dict(vote_th=0.8, scoring_method="ID", beta=1.0)
+            if set(bbox_vote) - set(opts):
+                raise K.KernelError("bbox_vote options: %s" % ", ".join(sorted(opts)))
+            opts.update(bbox_vote)
+            if opts["scoring_method"] not in K.VOTE_SCORING:
+                raise K.KernelError("unknown scoring method %r" % (opts["scoring_method"],))
+            if opts["scoring_method"] in ("TEMP_AVG", "GENERALIZED_AVG", "QUASI_SUM") and not opts["beta"] > 0:
+                raise K.KernelError("bbox_vote: beta must be positive for %s" % opts["scoring_method"])
+            post.vote, post.vote_thresh = 1, opts["vote_th"]
+            post.scoring_method, post.beta = K.VOTE_SCORING[opts["scoring_method"]], opts["beta"]
+        return post
 
     def __call__(self, cls_probs, box_preds, im_height, im_width, im_scale):
         for t, (h, w) in zip(cls_probs, self.shapes):
@@ -118,7 +161,7 @@ class RetinanetDetector(object):
                     not t.is_contiguous() or not t.is_cuda:
                 raise K.KernelError("box_pred must be 1 x A*4 x H x W contiguous float32 device tensors")
         PtrArr = C.c_void_p * self.levels
-        rc = K.lib().ssad_retinanet_detect(
+        args = (
             PtrArr(*[t.data_ptr() for t in cls_probs]), PtrArr(*[t.data_ptr() for t in box_preds]),
             C.c_void_p(self.cells.data_ptr()), self.levels, self.A, self.C, self.cfg.k_min, self._H,
             self._W, C.c_float(self.th), self.topn, C.c_float(self.nms), self.keep,
@@ -126,6 +169,10 @@ class RetinanetDetector(object):
             C.c_float(float(np.log(1000. / 16.))), C.c_void_p(self.out.data_ptr()),
             C.c_void_p(self.count.data_ptr()), C.c_void_p(self.ws.data_ptr()),
             C.c_size_t(self.ws.numel()), K._stream())
+        if self.post is None:
+            rc = K.lib().ssad_retinanet_detect(*args)
+        else:
+            rc = K.lib().ssad_retinanet_detect_ex(*args, C.byref(self.post))
         if rc:
             raise K.KernelError("retinanet_detect failed (%d)" % rc)
         return self.out[:int(self.count.item())]
