@@ -952,6 +952,57 @@ SSAD_API int ssad_gemm_f32(int trans_a, int trans_b, int M, int N, int K, float 
                            int ldc, long long stride_c, int batch, ssad_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* The softmax RetinaNet head (RETINANET.SOFTMAX)                          */
+/* GroupSpatialSoftmax  modules/detectron/group_spatial_softmax_op.cu:26-172 */
+/* SoftmaxFocalLoss     modules/detectron/softmax_focal_loss_op.cu:26-242  */
+/* (softmax_focal.hip).  C = classes per softmax group INCLUDING the        */
+/* background class 0, 2 <= C <= 128; a cell is one (image, anchor, y, x).  */
+/* ---------------------------------------------------------------------- */
+
+/* y = softmax over the C channels of every cell of x, N x (A*C) x H x W.  drop_background != 0: y is
+ * N x (A*(C-1)) x H x W and holds classes 1..C-1 only -- the scores RetinanetDetector / ssad_retinanet_detect
+ * take (core/test_retinanet.py:123-124) -- with the same bits as the full output.
+ * SSAD_E_BADARG, before any launch, for: a null pointer, C outside [2, 128], N, A, H or W <= 0. */
+SSAD_API int ssad_group_spatial_softmax(const float* x, float* y, int N, int A, int C, int H, int W,
+                                        int drop_background, ssad_stream_t stream);
+/* dx = y * (dy - sum_c y dy) per cell; y = the forward's full output.  Rejections as above. */
+SSAD_API int ssad_group_spatial_softmax_grad(const float* y, const float* dy, float* dx, int N, int A, int C,
+                                             int H, int W, ssad_stream_t stream);
+
+/* One FPN level: logits and prob N x D x H x W with D = A*C, labels N x A x H x W (-1 ignore, 0 background,
+ * 1..C-1 foreground class). */
+typedef struct ssad_softmax_focal_level {
+  const float* logits;     /* forward input; not read by the backward (may be NULL there) */
+  const int32_t* labels;
+  float* prob;             /* forward: output 1 of the op, written for every cell; backward: input */
+  float* out;              /* forward: the scalar loss; backward: dX (N x D x H x W) */
+  int N, D, H, W;
+} ssad_softmax_focal_level;
+
+/* bytes of scratch the forward needs for `n_levels` levels */
+SSAD_API size_t ssad_softmax_focal_loss_workspace_bytes(int n_levels);
+
+/* All levels in one launch + one fixed-order finalize launch:
+ *   prob = softmax(logits) per cell,
+ *   out[0] = scale * sum over cells with label >= 0 of -(1 - p)^gamma log(max(p, FLT_MIN)) z,
+ *   p = prob[label], z = [label == 0](1 - alpha)/Np + [label >= 1] alpha/Np, Np = max(fg_num[0], 1).
+ * params_host->num_classes is C here.  The result of a level does not depend on the other levels of the call.
+ * SSAD_E_BADARG, before any launch, for: a null pointer (levels, params, fg_num, a level's logits / labels /
+ * prob / out), C outside [2, 128], D <= 0 or D % C != 0, N, H or W <= 0, scale < 0, n_levels < 0 or
+ * > SSAD_MAX_LEVELS.  SSAD_E_WORKSPACE for a null workspace or one below
+ * ssad_softmax_focal_loss_workspace_bytes(n_levels).  n_levels == 0 returns 0 and launches nothing. */
+SSAD_API int ssad_softmax_focal_loss_forward(const ssad_softmax_focal_level* levels_host, int n_levels,
+                                             const float* fg_num, const ssad_focal_params* params_host,
+                                             void* workspace, size_t workspace_bytes, ssad_stream_t stream);
+/* out = dX = scale * dloss * w * ([c == label] - prob) for cells with label >= 0, 0 for the others, in one
+ * pass;  w = (-(1 - p)^gamma + gamma (1 - p)^(gamma - 1) p log(max(p, FLT_MIN))) z.  dloss: device scalars,
+ * one per level (dloss_stride = 0 to share one).  Rejections as the forward (no workspace; dloss null or
+ * dloss_stride < 0 is SSAD_E_BADARG). */
+SSAD_API int ssad_softmax_focal_loss_backward(const ssad_softmax_focal_level* levels_host, int n_levels,
+                                              const float* fg_num, const float* dloss, int dloss_stride,
+                                              const ssad_focal_params* params_host, ssad_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Introspection                                                           */
 /* ---------------------------------------------------------------------- */
 SSAD_API const char* ssad_kernels_arch(void);   /* "gfx950" */

@@ -42,6 +42,12 @@ class DistillLevel(C.Structure):
                 ("N", C.c_int), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int)]
 
 
+class SoftmaxFocalLevel(C.Structure):
+    """ssad_softmax_focal_level (include/ssad_kernels.h): one FPN level of the softmax focal loss."""
+    _fields_ = [("logits", C.c_void_p), ("labels", C.c_void_p), ("prob", C.c_void_p), ("out", C.c_void_p),
+                ("N", C.c_int), ("D", C.c_int), ("H", C.c_int), ("W", C.c_int)]
+
+
 class SmoothL1Level(C.Structure):
     _fields_ = [("Y_hat", C.c_void_p), ("Y", C.c_void_p), ("L", C.c_void_p), ("loss", C.c_void_p),
                 ("dY_hat", C.c_void_p), ("N", C.c_int), ("D", C.c_int), ("H", C.c_int),
@@ -150,6 +156,14 @@ def lib():
         C.POINTER(DistillLevel), i32, vp, vp, C.POINTER(DistillParams), C.POINTER(FocalParams),
         vp, vp, vp, sz, vp]
     L.ssad_cls_losses_fused_prezeroed.argtypes = L.ssad_cls_losses_fused.argtypes
+    L.ssad_group_spatial_softmax.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.ssad_group_spatial_softmax_grad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    L.ssad_softmax_focal_loss_workspace_bytes.restype = sz
+    L.ssad_softmax_focal_loss_workspace_bytes.argtypes = [i32]
+    L.ssad_softmax_focal_loss_forward.argtypes = [
+        C.POINTER(SoftmaxFocalLevel), i32, vp, C.POINTER(FocalParams), vp, sz, vp]
+    L.ssad_softmax_focal_loss_backward.argtypes = [
+        C.POINTER(SoftmaxFocalLevel), i32, vp, vp, i32, C.POINTER(FocalParams), vp]
     L.ssad_select_smooth_l1_workspace_bytes.restype = sz
     L.ssad_select_smooth_l1_workspace_bytes.argtypes = [i32]
     L.ssad_select_smooth_l1_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32,
@@ -409,6 +423,95 @@ def focal_loss_backward(levels, fg_num, dloss, *, gamma=1.0, alpha=0.25, num_cla
     stride = 1 if dloss.numel() >= n and n > 1 else 0
     _check(L.ssad_focal_loss_backward(arr, n, _ptr(fg_num), _ptr(dloss), stride, C.byref(P),
                                       _stream()), "focal_loss_backward")
+    return outs
+
+
+def _group_dims(x, num_classes, name):
+    _f32c(x, name)
+    if x.dim() != 4 or num_classes < 1 or x.shape[1] % num_classes != 0:
+        raise KernelError("%s must be N x (A*num_classes) x H x W, got %r for num_classes=%d"
+                          % (name, tuple(x.shape), num_classes))
+    N, D, H, W = x.shape
+    return N, D // num_classes, H, W
+
+
+def group_spatial_softmax(x, num_classes, drop_background=False, out=None):
+    """GroupSpatialSoftmax: softmax over each anchor's `num_classes` channels (background included) of
+    x [N, A*num_classes, H, W].  drop_background: the result holds classes 1.. only, [N, A*(num_classes-1), H, W]
+    -- the scores RetinanetDetector takes."""
+    N, A, H, W = _group_dims(x, num_classes, "logits")
+    shape = (N, A * (num_classes - (1 if drop_background else 0)), H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise KernelError("out must be %r, got %r" % (shape, tuple(out.shape)))
+    _check(lib().ssad_group_spatial_softmax(_ptr(x), _ptr(_f32c(out, "out")), N, A, num_classes, H, W,
+                                            int(bool(drop_background)), _stream()), "group_spatial_softmax")
+    return out
+
+
+def group_spatial_softmax_grad(y, dy, num_classes, out=None):
+    """dX = Y * (dY - sum_c Y dY) per (image, anchor, y, x); y = the full (background kept) probabilities."""
+    N, A, H, W = _group_dims(y, num_classes, "probabilities")
+    if _f32c(dy, "dy").shape != y.shape:
+        raise KernelError("dy must have the probabilities' shape")
+    dx = out if out is not None else torch.empty_like(y)
+    if _f32c(dx, "out").shape != y.shape:
+        raise KernelError("out must have the probabilities' shape")
+    _check(lib().ssad_group_spatial_softmax_grad(_ptr(y), _ptr(dy), _ptr(dx), N, A, num_classes, H, W, _stream()),
+           "group_spatial_softmax_grad")
+    return dx
+
+
+def _softmax_focal_levels(levels, probs, outs, need_logits):
+    arr = (SoftmaxFocalLevel * max(len(levels), 1))()
+    for i, ((x, g), p, o) in enumerate(zip(levels, probs, outs)):
+        if need_logits or x is not None:
+            _f32c(x, "logits")
+        ref = x if x is not None else p
+        if g.dtype != torch.int32 or not g.is_contiguous() or not g.is_cuda:
+            raise KernelError("labels must be a contiguous int32 device tensor")
+        if ref.dim() != 4 or _f32c(p, "prob").shape != ref.shape:
+            raise KernelError("logits / probabilities must be 4-D and equal-shaped")
+        N, D, H, W = ref.shape
+        if g.dim() != 4 or g.shape[0] != N or tuple(g.shape[2:]) != (H, W) or g.shape[1] == 0 \
+                or D % g.shape[1] != 0:
+            raise KernelError("labels must be N x A x H x W with A dividing the logits' channels, "
+                              "got %r for logits %r" % (tuple(g.shape), tuple(ref.shape)))
+        arr[i] = SoftmaxFocalLevel(x.data_ptr() if x is not None else 0, g.data_ptr(), p.data_ptr(),
+                                   o.data_ptr(), N, D, H, W)
+    return arr
+
+
+def softmax_focal_loss_forward(levels, fg_num, *, gamma=1.0, alpha=0.25, num_classes=81, scale=1.0, probs=None):
+    """SoftmaxFocalLoss; levels: list of (logits [N, A*num_classes, H, W], labels [N, A, H, W] int32);
+    num_classes counts the background.  Returns ([n_levels] losses, list of probabilities)."""
+    L = lib()
+    n = len(levels)
+    out = torch.empty(n, dtype=torch.float32, device="cuda")
+    if probs is None:
+        probs = [torch.empty_like(x) for x, _ in levels]
+    arr = _softmax_focal_levels(levels, probs, [out[i:i + 1] for i in range(n)], True)
+    P = FocalParams(gamma, alpha, num_classes, scale)
+    nb = L.ssad_softmax_focal_loss_workspace_bytes(n)
+    ws = _workspace(nb, "softmaxfocal")
+    _check(L.ssad_softmax_focal_loss_forward(arr, n, _ptr(fg_num), C.byref(P), _ptr(ws), nb, _stream()),
+           "softmax_focal_loss_forward")
+    return out, probs
+
+
+def softmax_focal_loss_backward(levels, probs, fg_num, dloss, *, gamma=1.0, alpha=0.25, num_classes=81,
+                                scale=1.0, out=None):
+    """levels as the forward's (the logits are not read and may be None), probs its second result; dloss: float32
+    device tensor with one value per level (or one shared).  Returns the list of dX tensors."""
+    L = lib()
+    n = len(levels)
+    outs = out if out is not None else [torch.empty_like(p) for p in probs]
+    arr = _softmax_focal_levels(levels, probs, outs, False)
+    P = FocalParams(gamma, alpha, num_classes, scale)
+    stride = 1 if dloss.numel() >= n and n > 1 else 0
+    _check(L.ssad_softmax_focal_loss_backward(arr, n, _ptr(fg_num), _ptr(dloss), stride, C.byref(P), _stream()),
+           "softmax_focal_loss_backward")
     return outs
 
 

@@ -44,6 +44,7 @@ class HeadConfig:
     temperature: float = 1.0
     use_cudnn_engine: bool = True         # the reference asks for engine=CUDNN
     fuse_relu: bool = False               # extension: fold Relu into the conv
+    softmax: bool = False                 # RETINANET.SOFTMAX: softmax head over num_classes (background kept)
 
     @property
     def num_anchors(self):
@@ -100,8 +101,20 @@ class HeadModel:
         return out
 
 
+class SoftmaxDistillError(ValueError):
+    """The adaptive distillation loss was asked of a softmax head: SigmoidAdaptiveDistillLoss takes
+    per-class sigmoid logits and teacher probabilities (A * (num_classes - 1) channels)."""
+
+
 def retinanet_bias_init(cfg):
-    """cls_pred bias so that sigmoid(b) = prior_prob (retinanet_heads.py:29-60)."""
+    """cls_pred bias so that sigmoid(b) = prior_prob (retinanet_heads.py:29-60); for the softmax head the
+    GivenTensorFill vector with log((C - 1)(1 - pi) / pi) on each anchor's background channel and 0 on the
+    others, so that softmax gives every foreground class pi / (C - 1) (:39-52)."""
+    if cfg.softmax:
+        bias = np.zeros((cfg.num_classes, 1), dtype=np.float32)
+        bias[0] = np.log((cfg.num_classes - 1) * (1 - cfg.prior_prob) / cfg.prior_prob)
+        bias = np.vstack([bias for _ in range(cfg.num_anchors)])
+        return ("GivenTensorFill", {"values": bias.astype(dtype=np.float32)})
     return ("ConstantFill", {"value": float(-np.log((1 - cfg.prior_prob) / cfg.prior_prob))})
 
 
@@ -115,9 +128,10 @@ def add_fpn_retinanet_outputs(model, blobs_in, dim_in, prefix=""):
     cfg = model.cfg
     assert len(blobs_in) == cfg.k_max - cfg.k_min + 1
     A = cfg.num_anchors
+    cls_pred_dim = cfg.num_classes if cfg.softmax else cfg.num_classes - 1      # retinanet_heads.py:78-80
     towers = (
         # (tower name, prediction blob stem, prediction width, prediction bias init)
-        ("cls", "retnet_cls_pred", (cfg.num_classes - 1) * A, retinanet_bias_init(cfg)),
+        ("cls", "retnet_cls_pred", cls_pred_dim * A, retinanet_bias_init(cfg)),
         ("bbox", "retnet_bbox_pred", 4 * A, ZERO),
     )
     feats = {}
@@ -135,7 +149,10 @@ def add_fpn_retinanet_outputs(model, blobs_in, dim_in, prefix=""):
             if tower == "cls":
                 preds[lvl][0] = _prediction(model, x, prefix + pred_stem, lvl, dim_in, pred_dim,
                                             pred_bias)
-                if not model.train:
+                if not model.train and cfg.softmax:
+                    model.net.GroupSpatialSoftmax(preds[lvl][0], prefix + "retnet_cls_prob_fpn%d" % lvl,
+                                                  num_classes=cls_pred_dim)
+                elif not model.train:
                     model.net.Sigmoid(preds[lvl][0], prefix + "retnet_cls_prob_fpn%d" % lvl)
         if tower == "bbox":
             for lvl in cfg.levels():
@@ -158,7 +175,7 @@ def _loss_gradients(model, loss_blobs):
 
 def add_fpn_retinanet_losses(model):
     """The student's supervised losses (retinanet_heads.py:259-307).  Their
-    operators (SelectSmoothL1Loss, SigmoidFocalLoss) are outside this build's
+    operators (SelectSmoothL1Loss, SigmoidFocalLoss or, for a softmax head, SoftmaxFocalLoss) are outside this build's
     hot path; the builder records them so the graph is complete."""
     cfg = model.cfg
     model.metrics += ["retnet_fg_num", "retnet_bg_num"]
@@ -173,6 +190,14 @@ def add_fpn_retinanet_losses(model):
         losses.append("retnet_loss_bbox_" + s)
     for lvl in cfg.levels():
         s = "fpn%d" % lvl
+        if cfg.softmax:                       # retinanet_heads.py:292-304
+            loss, _prob = model.net.SoftmaxFocalLoss(
+                ["retnet_cls_pred_" + s, "retnet_cls_labels_" + s, "retnet_fg_num"],
+                ["fl_" + s, "retnet_prob_" + s], gamma=cfg.focal_gamma, alpha=cfg.focal_alpha,
+                scale=cfg.loss_scale, num_classes=cfg.num_classes)
+            grads.append(loss)
+            losses.append("fl_" + s)
+            continue
         grads.append(model.net.SigmoidFocalLoss(
             ["retnet_cls_pred_" + s, "retnet_cls_labels_" + s, "retnet_fg_num"],
             ["fl_" + s], gamma=cfg.focal_gamma, alpha=cfg.focal_alpha, scale=cfg.loss_scale,
@@ -186,6 +211,9 @@ def add_distill_loss(model, student_prefix="", teacher_prefix="teacher/"):
     """PowSum normaliser over the teacher probabilities of all levels, then one
     SigmoidAdaptiveDistillLoss per level (retinanet_heads.py:313-352)."""
     cfg = model.cfg
+    if cfg.softmax:
+        raise SoftmaxDistillError("add_distill_loss: SigmoidAdaptiveDistillLoss does not take a softmax head "
+                                  "(HeadConfig.softmax); the reference's distillation loss is sigmoid-shaped too")
     normalizer = student_prefix + "retnet_fg_num"
     if cfg.adaptive_normalizer:
         normalizer = student_prefix + "distill_normalizer"

@@ -89,11 +89,18 @@ class RetinanetDetector(object):
     `soft_nms` = dict(method='linear' | 'gaussian' | 'hard', sigma=0.5, score_thresh=0.0001) replaces the greedy NMS
     by Soft-NMS (TEST.SOFT_NMS; the overlap threshold stays `nms_thresh`, test.py:783); `bbox_vote` =
     dict(vote_th=0.8, scoring_method='ID', beta=1.0) refines every survivor by box voting (TEST.BBOX_VOTE).  The
-    output is sorted by the final scores and cut at dets_per_im as before."""
+    output is sorted by the final scores and cut at dets_per_im as before.
+
+    `softmax=True` is the RETINANET.SOFTMAX head (test_retinanet.py:123-124 drops the background column before
+    the top-k): `__call__` then takes either the foreground probabilities [1][A*C][H][W] as above, or, with
+    `from_logits=True`, the raw cls_pred logits [1][A*(C+1)][H][W] (background first in every anchor's group),
+    which it turns into the former with kernels.group_spatial_softmax(drop_background=True) in buffers
+    allocated here."""
 
     def __init__(self, level_shapes, cfg=AnchorConfig, inference_th=0.05, pre_nms_topn=1000,
-                 nms_thresh=0.5, dets_per_im=100, device="cuda", *, soft_nms=None, bbox_vote=None):
+                 nms_thresh=0.5, dets_per_im=100, device="cuda", *, soft_nms=None, bbox_vote=None, softmax=False):
         self.post = self._post(soft_nms, bbox_vote)
+        self.softmax = self._softmax_args(softmax, False)
         self.cfg = cfg
         self.levels = len(level_shapes)
         self.A = cfg.scales_per_octave * len(cfg.aspect_ratios)
@@ -118,6 +125,18 @@ class RetinanetDetector(object):
         self.ws = torch.empty(int(nb), dtype=torch.uint8, device=device)
         self.out = torch.zeros((dets_per_im, 6), dtype=torch.float32, device=device)
         self.count = torch.zeros(1, dtype=torch.int32, device=device)
+        self._probs = [torch.empty((1, self.A * self.C, h, w), dtype=torch.float32, device=device)
+                       for h, w in level_shapes] if self.softmax else None
+
+    @staticmethod
+    def _softmax_args(softmax, from_logits):
+        """Checks the softmax= / from_logits= pair before the library is touched; returns bool(softmax)."""
+        if not isinstance(softmax, (bool, np.bool_)) or not isinstance(from_logits, (bool, np.bool_)):
+            raise K.KernelError("softmax= and from_logits= are booleans")
+        if from_logits and not softmax:
+            raise K.KernelError("from_logits=True needs a detector built with softmax=True (a sigmoid head's "
+                                "scores come from the cls_pred convolution's fused Sigmoid)")
+        return bool(softmax)
 
     @staticmethod
     def _post(soft_nms, bbox_vote):
@@ -151,7 +170,14 @@ class RetinanetDetector(object):
             post.scoring_method, post.beta = K.VOTE_SCORING[opts["scoring_method"]], opts["beta"]
         return post
 
-    def __call__(self, cls_probs, box_preds, im_height, im_width, im_scale):
+    def __call__(self, cls_probs, box_preds, im_height, im_width, im_scale, *, from_logits=False):
+        self._softmax_args(self.softmax, from_logits)
+        if from_logits:
+            for t, (h, w) in zip(cls_probs, self.shapes):
+                if tuple(t.shape) != (1, self.A * (self.C + 1), h, w):
+                    raise K.KernelError("cls_pred logits must be 1 x A*(C+1) x H x W")
+            cls_probs = [K.group_spatial_softmax(t, self.C + 1, drop_background=True, out=o)
+                         for t, o in zip(cls_probs, self._probs)]
         for t, (h, w) in zip(cls_probs, self.shapes):
             if tuple(t.shape) != (1, self.A * self.C, h, w) or t.dtype != torch.float32 or \
                     not t.is_contiguous() or not t.is_cuda:

@@ -67,12 +67,18 @@ def _feed(flat, name, arr):
     return True
 
 
-def initialize_from_weights_file(store, weights_file, teacher_weights_file=None):
+def initialize_from_weights_file(store, weights_file, teacher_weights_file=None, softmax=False):
     """Load student parameters (+ momentum) and, for distillation training, the
     teacher's parameters -- either from `teacher_weights_file` or from blobs the
     student file carries under `teacher/` (net.py:71-78).  `store`: the subnets
     (DistillHeads / FlatParams holder) or a whole NativeDistillModel, whose backbones
-    are then fed too.  Returns the lists of loaded and missing parameter names."""
+    are then fed too.  Returns the lists of loaded and missing parameter names.
+
+    softmax: the head is the RETINANET.SOFTMAX one -- `retnet_cls_pred_fpn<k_min>_w/_b` carry
+    A * num_classes output channels, background included (`store` is then a HeadParamStore of a
+    HeadConfig(softmax=True), or anything whose cls_pred parameters have that shape).  Without it a
+    softmax-shaped cls_pred blob is what it is to a sigmoid head: another shape, reported and skipped
+    -- also when the store itself is softmax-shaped, so a sigmoid pipeline is never fed by accident."""
     logger.info("Loading weights from: %s", weights_file)
     src, _ = _blobs_and_cfg(load_object(weights_file))
     src = dict(src)
@@ -83,12 +89,20 @@ def initialize_from_weights_file(store, weights_file, teacher_weights_file=None)
             src["teacher/" + k] = v
     if hasattr(store, "student") and hasattr(store, "heads"):
         return initialize_from_blobs(store, src)
-    return _initialize_heads(store, src, teacher_weights_file is not None)
+    return _initialize_heads(store, src, teacher_weights_file is not None, softmax=softmax)
 
 
-def _initialize_heads(store, src, teacher_file_given=False):
+def _softmax_store(store):
+    return bool(getattr(getattr(store, "cfg", None), "softmax", False))
+
+
+def _initialize_heads(store, src, teacher_file_given=False, softmax=False):
     loaded, missing = [], []
     used = set()
+    if softmax and not _softmax_store(store):
+        raise ValueError("softmax=True: the parameter store was not built for a softmax head "
+                         "(HeadParamStore(HeadConfig(softmax=True)))")
+    refuse_cls_pred = _softmax_store(store) and not softmax
     for name, _, _, _ in store.params.specs:
         if name not in src:
             logger.info("%s not found", name)
@@ -98,6 +112,10 @@ def _initialize_heads(store, src, teacher_file_given=False):
         mname = name + "_momentum"
         if mname in src:
             used.add(mname)
+        if refuse_cls_pred and name.startswith("retnet_cls_pred_"):
+            logger.info("Shape missmatch: name: %s is softmax-shaped %s; pass softmax=True to load it", name,
+                        tuple(np.asarray(src[name]).shape))
+            continue
         if not _feed(store.params, name, src[name]):
             continue            # net.py:106-109: a mismatching blob is skipped, momentum included
         loaded.append(name)
@@ -122,6 +140,55 @@ def _initialize_heads(store, src, teacher_file_given=False):
                 not k.startswith("teacher/"):
             preserved[k] = v
     return loaded, missing
+
+
+class _NamedParams(object):
+    """The `.specs` / `[name]` surface of head_pipeline.FlatParams over separate CPU tensors."""
+
+    def __init__(self, specs):
+        self.specs = list(specs)
+        self.views = OrderedDict((name, torch.zeros(tuple(shape), dtype=torch.float32))
+                                 for name, shape, _, _ in self.specs)
+
+    def __getitem__(self, name):
+        return self.views[name]
+
+
+class HeadParamStore(object):
+    """Host-side parameter store of the RetinaNet subnets as modeling.retinanet_heads builds them for `cfg` --
+    the softmax head (HeadConfig.softmax: cls_pred of A * num_classes channels) included: what
+    initialize_from_weights_file / save_model_to_weights_file need to carry a head's weights between a weights
+    file and the operator graph (feed `store.params[name]` for every name of `store.params.specs`).  No teacher:
+    the distillation loss does not take a softmax head."""
+
+    def __init__(self, cfg):
+        from ..modeling import retinanet_heads as rh
+        model = rh.HeadModel(cfg, train=True)
+        blobs = ["fpn_%d" % lvl for lvl in range(cfg.k_max, cfg.k_min - 1, -1)]
+        rh.add_fpn_retinanet_outputs(model, blobs, cfg.fpn_dim)
+        specs = [(name, tuple(shape), name.endswith("_b"), "late") for name, shape, _ in model.params]
+        self.cfg = cfg
+        self.fillers = OrderedDict((name, init) for name, _, init in model.params)
+        self.params, self.moms = _NamedParams(specs), _NamedParams(specs)
+        self.teacher = _NamedParams([])
+        self.distill = False
+        self.preserved = OrderedDict()
+
+    def fill(self, seed=0):
+        """Run the builder's fillers into `params`: GaussianFill(std), ConstantFill(value) and the softmax head's
+        GivenTensorFill(values) bias (retinanet_heads.py:39-60)."""
+        gen = torch.Generator().manual_seed(seed)
+        for name, (filler, kw) in self.fillers.items():
+            dst = self.params[name]
+            if filler == "GaussianFill":
+                dst.normal_(kw.get("mean", 0.0), kw.get("std", 1.0), generator=gen)
+            elif filler == "ConstantFill":
+                dst.fill_(kw.get("value", 0.0))
+            elif filler == "GivenTensorFill":
+                dst.copy_(torch.as_tensor(np.asarray(kw["values"], np.float32)).reshape(dst.shape))
+            else:
+                raise ValueError("HeadParamStore.fill: no filler %r (parameter %s)" % (filler, name))
+        return self
 
 
 def save_model_to_weights_file(weights_file, store, cfg_yaml=""):
