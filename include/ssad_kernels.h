@@ -377,10 +377,17 @@ SSAD_API int ssad_conv3x3_forward_wino24(
  *   amax_in  (device, n_levels words, or NULL): the inputs' |max| as float bit patterns, when a producer already
  *            measured them -- the |max| pass is skipped;
  *   amax_out (device, n_levels words the caller has zeroed, or NULL): the kernel folds the |max| of each level's
- *            OUTPUT into word l (atomicMax), ready to be the next layer's amax_in. */
+ *            OUTPUT into word l (atomicMax), ready to be the next layer's amax_in.
+ *   Work items: a level whose rows make an odd number of 8-row bands is cut into pairs of 8 x 16 half-tiles instead
+ *   of 16 x 16 tiles (bit-identical results, fewer padded rows multiplied); SSAD_SPLIT_HALF_TILES=0 in the
+ *   environment, read at every launch, forces 16 x 16 tiles everywhere.  ssad_conv3x3_split_items: the number of
+ *   (pixel tile, 128-channel block) items a launch with this level table and Cout works through (< 0: bad argument).
+ *   It is arithmetic over (N, H, W) and Cout only: the table's pointers are not read and nothing else that the launch
+ *   checks (workspace, packs, Cin) is validated. */
 SSAD_API size_t ssad_conv_split_filter_floats(int M, int K);
 SSAD_API int ssad_conv_split_pack_filters(const ssad_pack_entry* entries_host, int n_entries, ssad_stream_t stream);
 SSAD_API size_t ssad_conv3x3_split_workspace_bytes(const ssad_conv_level* levels_host, int n_levels, int Cin);
+SSAD_API int ssad_conv3x3_split_items(const ssad_conv_level* levels_host, int n_levels, int Cout);
 SSAD_API int ssad_conv3x3_forward_split(
     const ssad_conv_level* levels_host, int n_levels, const float* packed,
     const float* bias, int Cout, int Cin, int flags, void* workspace, size_t workspace_bytes,

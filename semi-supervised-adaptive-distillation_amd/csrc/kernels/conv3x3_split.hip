@@ -43,17 +43,20 @@ namespace {
 using namespace ssad_split;
 
 constexpr int TS = 16;                 // output tile edge
+constexpr int HT = TS / 2;             // rows of a half-tile: what one wave pair (wp) computes
 constexpr int HS = TS + 2;             // halo tile edge
+constexpr int HR = 2 * (HT + 2);       // halo rows of an LDS block: 18 of a full tile, or 2 x 10 of a pair of half-tiles
 constexpr int CBC = 2;                 // 8-channel blocks per K chunk (16 channels = one MFMA K)
-constexpr int SLOTS = CBC * HS * HS;   // 16-byte slots per plane and stage (648)
+constexpr int SLOTS = CBC * HR * HS;   // 16-byte slots per plane and stage (720)
 constexpr int NLD = 3;                 // LDS-DMA instructions per wave, plane and stage
-constexpr int STAGE = 4 * NLD * 64;    // stage pitch in slots (768: instruction k = 11 only lands zeros in the tail)
+constexpr int STAGE = 4 * NLD * 64;    // stage pitch in slots (768: the tail of instruction k = 11 only lands zeros)
 constexpr int AD = 9;                  // filter ring depth in taps = one chunk: the operands of (chunk c + 1, tap t) are requested
                                        // at the end of (chunk c, tap t); slot = tap, a compile-time constant
 constexpr int NBUF = 3;                // LDS stages: the halo of chunk c + 2 is requested during chunk c
 constexpr int MT = 128;                // output channels per workgroup
 constexpr int HDR = 16;                // floats in front of a packed filter: [0] = |max| of the filter (bits)
 static_assert(AD == 9 && NLD == 3, "the counted waits below are written for these");
+static_assert(SLOTS <= STAGE, "a plane's halo blocks fit the stage");
 
 #ifndef SPLIT_ABLATE     // debug builds (results wrong): 1 no halo DMA traffic, 2 no filter ring traffic, 4 only hi*hi
 #define SPLIT_ABLATE 0
@@ -142,19 +145,29 @@ struct SLevels {
   const float* w[kMaxLv];        // packed filter (header + planes)
   const float* bias[kMaxLv];
   int N[kMaxLv], H[kMaxLv], W[kMaxLv];
+  int half[kMaxLv];              // 1: the level's tiles are pairs of independent 8 x 16 half-tiles (below)
   int tile0[kMaxLv + 1];
   const unsigned* amax;          // [n_levels] |max| words of the inputs
   unsigned* amax_out;            // [n_levels] or null: |max| of the outputs is folded in (atomicMax; the caller zeroes)
   int n_levels, C, M, relu, sigmoid, mblocks, items;
 };
 
-// One work item = (16 x 16-pixel tile, 128-channel block).  The kernel is PERSISTENT (grid = #CUs, one workgroup of
-// four waves per CU = one wave per SIMD with the whole 512-entry register file: 128 accumulators, a filter ring one
-// chunk (9 taps x 4 operands = 144 registers) deep, 32 B-operand registers): a second workgroup per CU would cap a
-// wave at 256 registers, i.e. a 3-tap ring, and the in-order return of vector memory then parks the L2-resident filter
-// operands behind every halo fetch from HBM (measured: 0.7 of 2.1 ms).  What a second workgroup would have hidden is
-// hidden by hand instead: the next item's first two halo chunks and first nine filter taps are requested BEFORE the
-// current item's epilogue, three LDS stages let a halo chunk fly for more than a whole chunk of MFMAs.
+// One work item = (pixel tile, 128-channel block); a pixel tile = two 8-row x 16-column half-tiles, one per wave pair
+// wp, which reads the ten halo rows of its own half only.  Per level the host picks (level_half_mode below)
+//   full: the halves are the upper and lower 8 rows of one 16 x 16 tile and share its 18-row halo (LDS rows 0-17, wave
+//         base row 8 wp);
+//   half: the level's half-tiles (image, band of 8 rows, 16-column tile) are numbered flat over the whole batch and
+//         tile t is the halves 2 t and 2 t + 1 -- two images' worth if it falls that way, an empty half at an odd end;
+//         half p owns LDS rows 10 p ... 10 p + 9 (wave base row 10 wp).  Pays where ceil(H / 8) is odd: a 16-row tile
+//         would multiply 8 rows of padding per column of tiles.
+// Every output's sum is formed in the same chunk, tap and MFMA order either way: the results are bit-identical.
+// The kernel is PERSISTENT (grid = #CUs, one workgroup of four waves per CU = one wave per SIMD with the whole
+// 512-entry register file: 128 accumulators, a filter ring one chunk (9 taps x 4 operands = 144 registers) deep, 32
+// B-operand registers): a second workgroup per CU would cap a wave at 256 registers, i.e. a 3-tap ring, and the
+// in-order return of vector memory then parks the L2-resident filter operands behind every halo fetch from HBM
+// (measured: 0.7 of 2.1 ms).  What a second workgroup would have hidden is hidden by hand instead: the next item's
+// first two halo chunks and first nine filter taps are requested BEFORE the current item's epilogue, three LDS stages
+// let a halo chunk fly for more than a whole chunk of MFMAs.
 template <bool MASKED>
 __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevels q) {
   __shared__ uint4 lds[NBUF * 2 * STAGE];        // [buffer][plane][STAGE]
@@ -168,12 +181,28 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
   const int nchunks = (CB + CBC - 1) / CBC;
   const unsigned w_lo_off = (unsigned)(9LL * CB * M * 16);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr)lds;
-  const int brow = wp * 8 + (j >> 4), bcol = (j & 16) ? ((j - 2) & 15) : j;
-  const int bbase = (h * HS + brow) * HS + bcol;           // + (2 tt + dy) * HS + dx
+  const int bcol = (j & 16) ? ((j - 2) & 15) : j;
+  const int bbase0 = (h * HR + (j >> 4)) * HS + bcol;      // + the wave's base row (per item) + (2 tt + dy) * HS + dx
 
   // ---- the item under the LOADER's cursor (one item ahead of the compute side between prologue and epilogue)
   struct Item {
-    int lv, n, y0, x0, ocb, H, W, N;
+    int lv, ocb, H, W, N, half;
+    int n0, y0, x0, n1, y1, x1;  // the two half-tiles; an empty one has y > H
+  };
+  // what the compute side and the epilogue keep of an item: the level and the wave's own half (wp).  Only bind() needs
+  // both halves, so they are not carried through the chunk loop; the level's extent is read again from the argument
+  // block in the epilogue (fewer live scalars across the loop, where a spilled one costs a restore per chunk).
+  struct Own {
+    int lv, ocb;
+    int n, y0, x0;               // the half this wave computes and stores
+    int boff;                    // LDS slot of its first halo row: row 8 wp (full) or 10 wp (half)
+  };
+  auto own = [&](const Item& I) {
+    Own o;
+    o.lv = I.lv; o.ocb = I.ocb;
+    o.n = wp ? I.n1 : I.n0; o.y0 = wp ? I.y1 : I.y0; o.x0 = wp ? I.x1 : I.x0;
+    o.boff = wp * (I.half ? HT + 2 : HT) * HS;
+    return o;
   };
   auto decode = [&](int it) {
     // item id -> (tile, output-channel block): ids b, b + 8, ... share an XCD's L2; the channel blocks of one tile are
@@ -187,12 +216,24 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
       if (t >= q.tile0[l]) lv = l;
     o.lv = t < q.tile0[q.n_levels] ? lv : -1;              // (the id space is padded to a multiple of 8 tiles)
     o.N = q.N[lv]; o.H = q.H[lv]; o.W = q.W[lv];
-    const int tiles_x = (o.W + TS - 1) / TS, tiles_y = (o.H + TS - 1) / TS;
+    o.half = q.half[lv];
+    const int tiles_x = (o.W + TS - 1) / TS, tiles_y = o.half ? (o.H + HT - 1) / HT : (o.H + TS - 1) / TS;
     t -= q.tile0[lv];
-    const int tx = t % tiles_x; t /= tiles_x;
-    const int ty = t % tiles_y;
-    o.n = t / tiles_y;
-    o.y0 = ty * TS; o.x0 = tx * TS;
+    if (o.half) t *= 2;
+    int tx = t % tiles_x; t /= tiles_x;
+    int ty = t % tiles_y;
+    int n = t / tiles_y;
+    o.n0 = n; o.x0 = tx * TS;
+    if (o.half) {
+      o.y0 = ty * HT;
+      // the next half in the flat order; past the last image: empty (every row out of range, nothing stored)
+      if (++tx == tiles_x) { tx = 0; if (++ty == tiles_y) { ty = 0; ++n; } }
+      const bool any = n < o.N;
+      o.n1 = any ? n : 0; o.y1 = any ? ty * HT : o.H + HT; o.x1 = tx * TS;
+    } else {
+      o.y0 = ty * TS;
+      o.n1 = n; o.y1 = o.y0 + HT; o.x1 = o.x0;
+    }
     o.ocb = mb * MT;
     return o;
   };
@@ -205,17 +246,21 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
     x_lo_off = (unsigned)((long long)I.N * CB * plane16);          // bytes from the hi to the lo plane
     xrs = ssad_dev::uniform_rsrc_words(q.x[I.lv], 2u * x_lo_off);
     wrs = ssad_dev::uniform_rsrc_words(q.w[I.lv] + HDR, 2u * w_lo_off);
-    // halo staging by LDS-DMA: slot s = (block, row, col) of the 18 x 18 x 2-block tile of one plane; wave-level
+    // halo staging by LDS-DMA: slot s = (block, row, col) of the 20 x 18 x 2-block tile of one plane; wave-level
     // instruction k writes slots [64 k, 64 k + 64) of a plane's stage; wave w issues k = w, w + 4, w + 8 per plane.
-    // Lanes outside the image / past the last slot go to an out-of-range offset (zero fill).
+    // Full mode: rows 0-17 are the tile's halo, rows 18-19 stay empty; half mode: rows 10 p ... 10 p + 9 are the halo
+    // of half p, addressed from that half's own (image, y0, x0).  Lanes outside the image / past the last slot go to
+    // an out-of-range offset (zero fill).
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int s = 64 * (wave + 4 * i) + lane;
-      const int cbl = s / (HS * HS), r = s % (HS * HS);
-      const int gy = I.y0 - 1 + r / HS, gx = I.x0 - 1 + r % HS;
-      const bool ok = s < SLOTS && gy >= 0 && gy < I.H && gx >= 0 && gx < I.W;
+      const int cbl = s / (HR * HS), r = s % (HR * HS);
+      const int row = r / HS, col = r % HS;
+      const bool p = I.half && row >= HT + 2;              // the slot's half
+      const int gy = (p ? I.y1 - (HT + 2) : I.y0) - 1 + row, gx = (p ? I.x1 : I.x0) - 1 + col;
+      const bool ok = s < SLOTS && (I.half || row < HS) && gy >= 0 && gy < I.H && gx >= 0 && gx < I.W;
       dcb[i] = cbl;
-      dvo[i] = ok ? (unsigned)((((long long)I.n * CB + cbl) * plane + (long long)gy * I.W + gx) * 16) : kOob;
+      dvo[i] = ok ? (unsigned)((((long long)(p ? I.n1 : I.n0) * CB + cbl) * plane + (long long)gy * I.W + gx) * 16) : kOob;
     }
     // A: Wp[tap][cb][m] x 16 B; lane = (row m, 8-channel block h).  Rows past M are clamped (never stored).
 #pragma unroll
@@ -268,11 +313,12 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
 
   const int G = (int)gridDim.x;
   int it = (int)blockIdx.x;
-  Item cur = decode(it);
+  Item first = decode(it);
   // (ids past the padded id space never occur: grid <= items; an id inside the padding has lv = -1 and is skipped)
-  while (it < q.items && cur.lv < 0) { it += G; if (it < q.items) cur = decode(it); }
+  while (it < q.items && first.lv < 0) { it += G; if (it < q.items) first = decode(it); }
   if (it >= q.items) return;
-  bind(cur);
+  bind(first);
+  Own cur = own(first);
   prologue();
   ring_landed();
   __builtin_amdgcn_s_barrier();
@@ -296,6 +342,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
     }
 
     int buf = gbuf;                               // stage of chunk c
+    const int bbase = bbase0 + cur.boff;
     for (int c = 0; c < nchunks; ++c) {
       const bool more = c + 1 < nchunks, more2 = c + 2 < nchunks;
       int buf2 = buf + 2; if (buf2 >= NBUF) buf2 -= NBUF;
@@ -381,20 +428,22 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
     // ---- hand-over: the next item's first loads fly during this item's epilogue.  (Nothing real of THIS item is in
     // flight: the last chunks' refills / pieces were out of range; the zero fill they wrote into the stages the next
     // prologue targets retires before it -- same wave, same slots, in order.)
-    const Item done = cur;
+    const Own done = cur;
     int nit = it + G;
-    Item nxt = done;
+    Item nxt{};
     while (nit < q.items) { nxt = decode(nit); if (nxt.lv >= 0) break; nit += G; }
     const bool have_next = nit < q.items;
+    const Own nown = own(nxt);
     // what the epilogue needs of the finished item, before the loader's state moves on
-    const long long plane = (long long)done.H * done.W;
+    const int doneH = q.H[done.lv], doneW = q.W[done.lv];
+    const long long plane = (long long)doneH * doneW;
     const int oc_w = done.ocb + wo * 64;
     unsigned pvo[4];
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
-      const int gy = done.y0 + wp * 8 + 2 * tt + (j >> 4), gx = done.x0 + bcol;
-      const bool okp = gy < done.H && gx < done.W;
-      const long long pix = (long long)gy * done.W + gx;
+      const int gy = done.y0 + 2 * tt + (j >> 4), gx = done.x0 + bcol;
+      const bool okp = gy < doneH && gx < doneW;
+      const long long pix = (long long)gy * doneW + gx;
       pvo[tt] = okp ? (unsigned)((((long long)done.n * M + 4 * h) * plane + pix) * 4) : kOob;
     }
     SDBG(itn, 2);
@@ -415,7 +464,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
       const bool one_scale = e2 >= -126 && e2 <= 127;
       const float sc1 = one_scale ? pow2f(e2) : pow2f(split_exponent(q.amax[lv]) - 15);
       const float sc2 = one_scale ? 1.0f : pow2f(split_exponent(reinterpret_cast<const unsigned*>(q.w[lv])[0]) - 15);
-      const unsigned ybytes = (unsigned)((long long)done.N * M * plane * 4);
+      const unsigned ybytes = (unsigned)((long long)q.N[lv] * M * plane * 4);
       const __amdgpu_buffer_rsrc_t yrs = uniform_rsrc(q.y[lv], ybytes);
       const __amdgpu_buffer_rsrc_t mrs = uniform_rsrc(MASKED ? (const void*)q.aux[lv] : (const void*)q.y[lv], ybytes);
       const float* bias = q.bias[lv];
@@ -481,6 +530,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
 #endif
     if (!have_next) {
       if (q.amax_out) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the waves' wg_max words are written
         __builtin_amdgcn_s_barrier();
         if (tid == 0) {
           unsigned m = wg_max[0];
@@ -494,6 +544,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
     SDBG(itn, 4);
     ring_landed();
     SDBG(itn, 5);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // wg_max: written before the barrier, read behind it
     __builtin_amdgcn_s_barrier();
     SDBG(itn, 6);
 #ifdef SPLIT_TIMELINE
@@ -505,7 +556,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_split_kernel(const SLevel
       if (m) atomicMax(q.amax_out + done.lv, m);
     }
     it = nit;
-    cur = nxt;
+    cur = nown;
   }
 }
 
@@ -530,6 +581,19 @@ int make_plan(const ssad_conv_level* lv, int n_levels, int Cin, Plan* p) {
   }
   p->total_bytes = off;
   return 0;
+}
+
+// SSAD_SPLIT_HALF_TILES=0 forces full mode on every level (A/B runs, the bit-identity test); read at every launch.
+bool half_tiles_enabled() {
+  const char* e = getenv("SSAD_SPLIT_HALF_TILES");
+  return !(e && *e) || atoi(e) != 0;
+}
+// A level runs in half mode when its rows make an odd number of 8-row bands: only then do 16-row tiles multiply a
+// whole band of padding (P4, P5, P7, res4, res5 at 600 px; with an even count the halves would only cost halo traffic).
+bool level_half_mode(const ssad_conv_level& l, bool enabled) { return enabled && (cdiv(l.H, HT) & 1); }
+// pixel tiles (full mode) or pairs of half-tiles (half mode) of a level
+int level_tiles(const ssad_conv_level& l, bool half) {
+  return half ? cdiv(l.N * cdiv(l.H, HT) * cdiv(l.W, TS), 2) : l.N * cdiv(l.H, TS) * cdiv(l.W, TS);
 }
 
 }  // namespace
@@ -578,6 +642,20 @@ size_t ssad_conv3x3_split_workspace_bytes(const ssad_conv_level* lv, int n_level
   return p.total_bytes;
 }
 
+// Pure arithmetic over (N, H, W) and Cout: the level table's pointers are not read, and a count says nothing about
+// whether the launch itself would be accepted (workspace, packs, the 32-bit offset limits that depend on Cin).
+int ssad_conv3x3_split_items(const ssad_conv_level* lv, int n_levels, int Cout) {
+  if (!lv || n_levels < 1 || n_levels > kMaxLv || Cout <= 0) return SSAD_E_BADARG;
+  const bool halves = half_tiles_enabled();
+  long long tiles = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    if (lv[l].N < 0 || lv[l].H < 0 || lv[l].W < 0) return SSAD_E_BADARG;
+    if ((long long)lv[l].N * lv[l].H * lv[l].W * Cout >= (1LL << 29)) return SSAD_E_BADARG;
+    tiles += level_tiles(lv[l], level_half_mode(lv[l], halves));
+  }
+  return (int)(tiles * cdiv(Cout, MT));
+}
+
 int ssad_conv3x3_forward_split(const ssad_conv_level* lv, int n_levels, const float* packed, const float* bias,
                                int Cout, int Cin, int flags, void* workspace, size_t workspace_bytes,
                                const unsigned* amax_in, unsigned* amax_out, ssad_stream_t stream_) {
@@ -597,6 +675,7 @@ int ssad_conv3x3_forward_split(const ssad_conv_level* lv, int n_levels, const fl
   q.amax_out = amax_out;
   pt.C = Cin;
   int nl = 0, ablocks = 0, pblocks = 0, tiles = 0;
+  const bool halves = half_tiles_enabled();
   for (int l = 0; l < n_levels; ++l) {
     const float* pk = lv[l].packed ? lv[l].packed : packed;
     if (!pk) return SSAD_E_BADARG;
@@ -627,8 +706,9 @@ int ssad_conv3x3_forward_split(const ssad_conv_level* lv, int n_levels, const fl
     q.w[nl] = pk;
     q.bias[nl] = lv[l].packed ? lv[l].bias : bias;
     q.N[nl] = lv[l].N; q.H[nl] = lv[l].H; q.W[nl] = lv[l].W;
+    q.half[nl] = level_half_mode(lv[l], halves) ? 1 : 0;
     q.tile0[nl] = tiles;
-    tiles += lv[l].N * cdiv(lv[l].H, TS) * cdiv(lv[l].W, TS);
+    tiles += level_tiles(lv[l], q.half[nl] != 0);
     ++nl;
   }
   if (nl == 0) return 0;
@@ -639,7 +719,7 @@ int ssad_conv3x3_forward_split(const ssad_conv_level* lv, int n_levels, const fl
   for (int l = nl; l < kMaxLv; ++l) {
     at.x[l] = pt.x[l] = nullptr; at.n[l] = 0; pt.planes[l] = nullptr; pt.N[l] = 0; pt.plane[l] = 0;
     q.x[l] = nullptr; q.y[l] = nullptr; q.aux[l] = nullptr; q.w[l] = nullptr; q.bias[l] = nullptr;
-    q.N[l] = q.H[l] = q.W[l] = 0;
+    q.N[l] = q.H[l] = q.W[l] = q.half[l] = 0;
     if (l > nl) { at.block_start[l] = ablocks; pt.block_start[l] = pblocks; q.tile0[l] = tiles; }
   }
   q.C = Cin; q.M = Cout;

@@ -225,6 +225,7 @@ def lib():
     L.ssad_conv_split_pack_filters.argtypes = [C.POINTER(PackEntry), i32, vp]
     L.ssad_conv3x3_split_workspace_bytes.restype = sz
     L.ssad_conv3x3_split_workspace_bytes.argtypes = [C.POINTER(ConvLevel), i32, i32]
+    L.ssad_conv3x3_split_items.argtypes = [C.POINTER(ConvLevel), i32, i32]
     L.ssad_conv3x3_forward_split.argtypes = [C.POINTER(ConvLevel), i32, vp, vp, i32, i32, i32, vp, sz, vp, vp, vp]
     L.ssad_conv3x3_forward_wino_launches.argtypes = [C.POINTER(ConvLevel), i32]
     L.ssad_conv3x3_forward_wino_launches_for.argtypes = [C.POINTER(ConvLevel), i32, i32, i32, i32]
@@ -847,6 +848,17 @@ def conv3x3_forward_split(xs, packed, bias, Cout, *, relu=False, sigmoid=False, 
                                         workspace.numel(), _ptr(amax_in), _ptr(amax_out), _stream()),
            "conv3x3_forward_split")
     return ys
+
+
+def conv3x3_split_items(shapes, Cout):
+    """Work items (pixel tiles or pairs of half-tiles x 128-channel blocks) of a split-engine launch over levels of the
+    given (N, H, W); follows SSAD_SPLIT_HALF_TILES like the launch itself.  Host arithmetic only."""
+    arr = (ConvLevel * len(shapes))()
+    for i, (N, H, W) in enumerate(shapes):
+        arr[i] = ConvLevel(0, 0, 0, N, H, W, 0, 0)
+    n = lib().ssad_conv3x3_split_items(arr, len(shapes), Cout)
+    _check(min(n, 0), "conv3x3_split_items")
+    return n
 
 
 def conv3x3_forward_wino24(xs, packed, bias, Cout, *, relu=False, sigmoid=False, out=None, mask_by=None):
