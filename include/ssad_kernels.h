@@ -790,6 +790,65 @@ SSAD_API int ssad_retinanet_detect_ex(
     int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
     const ssad_detect_post* post);
 
+/* COCO box evaluation on the device (detectron/lib/datasets/vid_eval.py: evaluateImg :236-318, accumulate
+ * :320-425; driven for boxes by vid_dataset_evaluator.py:192-197).  useCats = 1, iouType 'bbox' only.
+ *
+ * Layout.  Every image owns `cap` detection slots: det_xywh [I][cap][4] double, det_score [I][cap] double,
+ * det_cat [I][cap] int (0-based category, -1 = empty slot).  Ground truth is sorted by cell = image * K + category
+ * (stable) on the host: gt_xywh [G][4] double, gt_area [G] double, gt_crowd [G] uint8, gt_cell_off [I*K + 1] int.
+ * p = a * T + t numbers the (area range, IoU threshold) pairs; each is one lane's independent greedy walk.
+ *
+ * ssad_coco_eval_add fills the slots of one image from float32 rows: x = x1, y = y1, w = x2 - x1 + 1 and
+ * h = y2 - y1 + 1 in float32, then widened (json_dataset_evaluator.py:179 through utils/boxes.py xyxy_to_xywh); slots
+ * n ... cap-1 are emptied.  The category is cats_i32[j] or, where that is NULL, (int)cls1_f32[j * cls_stride] - 1
+ * (the detector's 1-based class column).  A category outside [0, K) is counted in bad_count[0] and its slot emptied.
+ * n > cap is SSAD_E_BADARG.
+ *
+ * ssad_coco_eval_match: one workgroup per cell.
+ *   - detections of the cell by score descending, equal scores in slot order, cut at max_det (<= SSAD_COCO_EVAL_MAX_DETS,
+ *     else SSAD_E_BADARG): det_rank [I][cap] int = position in that order, -1 for cut / empty slots;
+ *   - per p: a ground truth is ignored when crowd or area outside [lo, hi]; non-ignored first, ignored last, each in
+ *     the given order; the walk of vid_eval.py:274-301 with float64 box IoU recomputed on the way
+ *     (w = min(dx+dw, gx+gw) - max(dx, gx), h likewise, 0 unless both > 0, union = dw*dh + gw*gh - i, or dw*dh alone
+ *     for a crowd; no fused multiply-add anywhere), small_box_relax != 0 applying :286-288's
+ *     tiou = min(iou, w*h / ((w+10)*(h+10))) and 0 the COCO toolbox's tiou = iou;
+ *   - dt_match [I][cap][A*T] int = matched ground truth as index + 1 within its cell, 0 for none; dt_ignore
+ *     [I][cap][A*T] uint8 (the match's ignore flag, or for an unmatched detection: w*h outside the range); both are
+ *     written for slots with det_rank >= 0 only;
+ *   - cell_npig [I*K][A] int = non-ignored ground truths, cell_eval [I*K] uint8 = the cell has any ground truth or
+ *     any detection.
+ *   Ground truths per cell are unbounded: the per-walk matched flags live in the workspace (G * A * T bytes).
+ *
+ * ssad_coco_eval_accumulate: `perm` [n_perm] int64 lists slots (image * cap + j) ordered by category, then score
+ * descending, then image, then det_rank -- the reference's stable mergesort of the per-image lists concatenated in
+ * image order; seg [K + 1] int64 bounds each category's run in it (slots with det_rank < 0 lie outside every run).
+ * Per (category, area range, maxDets entry, threshold): tp / fp running counts over the run's slots with
+ * det_rank < max_dets[m], rc = tp / npig, pr = tp / (fp + tp + eps), right-to-left running maximum, and for every
+ * rec_thrs[r] (ascending) the first position with rc >= rec_thrs[r]: precision / scores [T][R][K][A][M] double there,
+ * 0 past the end; recall [T][K][A][M] = the last rc (0 without detections).  -1 everywhere for a category without an
+ * evaluated cell or with npig == 0.  iou_thrs / rec_thrs are the host's arrays: nothing is recomputed here. */
+#define SSAD_COCO_EVAL_MAX_DETS 1024
+SSAD_API int ssad_coco_eval_add(const float* boxes_xyxy, int box_stride, const float* scores, int score_stride,
+                                const float* cls1_f32, int cls_stride, const int* cats_i32, int n, int cap, int K,
+                                int image, double* det_xywh, double* det_score, int* det_cat, int* bad_count,
+                                ssad_stream_t stream);
+SSAD_API size_t ssad_coco_eval_match_workspace_bytes(long long G, int A, int T);
+SSAD_API int ssad_coco_eval_match(int I, int K, int cap, const double* det_xywh, const double* det_score,
+                                  const int* det_cat, const double* gt_xywh, const double* gt_area,
+                                  const unsigned char* gt_crowd, const int* gt_cell_off, long long G,
+                                  const double* iou_thrs, int T, const double* area_rng, int A, int max_det,
+                                  int small_box_relax, int* det_rank, int* dt_match, unsigned char* dt_ignore,
+                                  int* cell_npig, unsigned char* cell_eval, void* workspace, size_t workspace_bytes,
+                                  ssad_stream_t stream);
+SSAD_API size_t ssad_coco_eval_accumulate_workspace_bytes(int K, int A);
+SSAD_API int ssad_coco_eval_accumulate(int I, int K, int cap, int A, int T, int M, int R, const int* max_dets,
+                                       const long long* perm, long long n_perm, const long long* seg,
+                                       const double* det_score, const int* det_rank, const int* dt_match,
+                                       const unsigned char* dt_ignore, const int* cell_npig,
+                                       const unsigned char* cell_eval, const double* rec_thrs, double* precision,
+                                       double* scores, double* recall, void* workspace, size_t workspace_bytes,
+                                       ssad_stream_t stream);
+
 /* ---------------------------------------------------------------------- */
 /* fp16 storage / fp32 accumulation (BASELINE config 5's precision)        */
 /* ---------------------------------------------------------------------- */
