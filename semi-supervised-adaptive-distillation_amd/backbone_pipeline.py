@@ -42,6 +42,7 @@ import torch
 from . import kernels as K
 from . import program as PR
 from .data_parallel import BucketedAllReduce
+from .modeling.resnet_fpn import ChannelRatioError, channel_widths
 
 # pixels (all images) a pointwise launch needs before the split-operand GEMM pays (see NativeResNetFPN._gemm)
 GEMM_SPLIT_MIN_PIXELS = 8192
@@ -50,6 +51,23 @@ ARCHS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3)
 # ResNeXt (ResNet.py:247-258): name -> (groups, width per group); the stride sits on the 3x3
 # (RESNETS.STRIDE_1X1 = False).  Forward only: it is the frozen teacher of BASELINE config 5.
 GROUPED = {"x101-64x4d": (64, 4)}
+
+
+def student_widths(arch, channel_ratio, fpn_dim=256):
+    """Widths of a network of RESNETS.CHANNEL_RATIO = channel_ratio (modeling.resnet_fpn.channel_widths: the
+    reference's expressions, truncation included) after the checks that need no device: a ratio other than 1 is for
+    the plain ResNets (the grouped 3x3 kernel is written for the ResNeXt teacher's widths) and must give widths that
+    are positive multiples of 16.  Raises KernelError."""
+    if arch not in ARCHS:
+        raise K.KernelError("native backbone: architectures %s" % sorted(ARCHS))
+    groups, width = GROUPED.get(arch, (1, 64))
+    if float(channel_ratio) != 1.0 and arch in GROUPED:
+        raise K.KernelError("native backbone: channel_ratio %r with the grouped architecture %s is not supported "
+                            "(the grouped 3x3 kernel serves the full-width ResNeXt teacher only)" % (channel_ratio, arch))
+    try:
+        return channel_widths(channel_ratio, groups, width, fpn_dim)
+    except ChannelRatioError as e:
+        raise K.KernelError("native backbone: %s" % e)
 
 
 class _Layer(object):
@@ -72,14 +90,21 @@ class _Layer(object):
 class NativeResNetFPN(object):
     def __init__(self, arch="r50", N=2, image_hw=(640, 896), device="cuda", train=True, src=None,
                  fpn_dim=256, lr=1e-5, momentum=0.9, weight_decay=1e-4, process_group=None, world_size=1,
-                 affine_scales=None, skip_flag=None, overlap_wgrad=None):
-        if arch not in ARCHS:
-            raise K.KernelError("native backbone: architectures %s" % sorted(ARCHS))
+                 affine_scales=None, skip_flag=None, overlap_wgrad=None, channel_ratio=1.0):
+        """channel_ratio: RESNETS.CHANNEL_RATIO (ResNet.py:99-124, FPN.py:122,501), the width multiplier of a thin
+        student; fpn_dim is FPN.DIM before the ratio, self.D = int(fpn_dim * channel_ratio) what the network builds
+        (and the subnets inherit).  The stem stays 64 wide."""
+        if float(channel_ratio) != 1.0 and getattr(self, "F16", False):
+            raise K.KernelError("native backbone: channel_ratio %r with the fp16-storage backbone is not supported "
+                                "(backbone_f16's kernels were written for the full widths); use the fp32 backbone"
+                                % (channel_ratio,))
+        self.widths = student_widths(arch, channel_ratio, fpn_dim)       # (before anything touches the library)
+        self.channel_ratio = float(channel_ratio)
         if arch in GROUPED and train:
             raise K.KernelError("native backbone: %s is forward only (the frozen teacher); its grouped 3x3 has no "
                                 "gradient kernels" % arch)
         self.arch, self.N, self.hw, self.device, self.train = arch, N, tuple(image_hw), device, train
-        self.D = fpn_dim
+        self.D = self.widths.fpn_dim
         self.momentum, self.weight_decay = momentum, weight_decay
         self.dp = BucketedAllReduce(process_group, world_size)
         self.timing = None
@@ -98,6 +123,18 @@ class NativeResNetFPN(object):
         self._overlap_wgrad = overlap_wgrad
         self._build()
 
+    @classmethod
+    def layer_shapes(cls, arch, channel_ratio=1.0, fpn_dim=256):
+        """{layer name: filter shape (cout, cin / group, k, k)} of the network, without building it (utils/net.py
+        checks a weights file against it before anything is allocated)."""
+        nat = cls.__new__(cls)
+        nat.arch, nat.train = arch, False
+        nat.widths = student_widths(arch, channel_ratio, fpn_dim)
+        nat.D = nat.widths.fpn_dim
+        nat._layers = OrderedDict()
+        nat._define_layers()
+        return OrderedDict((n, (l.cout, l.wcin, l.k, l.k)) for n, l in nat._layers.items())
+
     # -- network definition -------------------------------------------------------------
     def _define_layers(self):
         L = self._layers
@@ -106,14 +143,18 @@ class NativeResNetFPN(object):
             L[name] = _Layer(name, k, cin, cout, stride, train and self.train, group,
                              affine=name.startswith(("stem", "res")))
         groups, width = GROUPED.get(self.arch, (1, 64))
-        add("stem.0", 7, 3, 64, 2, train=False)
-        cin = 64
+        wd = getattr(self, "widths", None) or channel_widths(1.0, groups, width, self.D)
+        add("stem.0", 7, 3, wd.stem, 2, train=False)
+        cin = wd.stem
         self.blocks = []                       # (stage, j, cin, cmid, cout, stride, has_proj, trainable)
         for si, nblk in enumerate(ARCHS[self.arch]):
             stage = si + 2
-            cmid, cout = groups * width * 2 ** si, 256 * 2 ** si
+            cmid, cout = wd.inner[si], wd.stage[si]
             tr = stage > 2                     # FREEZE_AT = 2: the stem and res2 stay frozen
             for j in range(nblk):
+                # by stage index.  (ResNet.py:173-175 tells the first stage by dim_in == 64; at ratio 0.25 res2 also
+                # leaves 64 channels and the reference's res3_0 gets stride 1 -- its levels then disagree with its own
+                # anchor strides.  Not restated here: P3..P7 stay at strides 8..128.  DESIGN 3.13.)
                 stride = 2 if (j == 0 and si > 0) else 1
                 pre = "res%d.%d" % (stage, j)
                 s1, s3 = (stride, 1) if groups == 1 else (1, stride)        # STRIDE_1X1
@@ -125,11 +166,11 @@ class NativeResNetFPN(object):
                     add(pre + ".proj", 1, cin, cout, stride, tr)
                 self.blocks.append((stage, j, cin, cmid, cout, stride, proj, tr and self.train))
                 cin = cout
-        for i, c in enumerate((2048, 1024, 512)):
+        for i, c in enumerate(reversed(wd.stage[1:])):           # res5, res4, res3
             add("lat.%d" % i, 1, c, self.D)
         for i in range(3):
             add("out.%d" % i, 3, self.D, self.D)
-        add("p6", 3, 2048, self.D, 2)
+        add("p6", 3, wd.stage[3], self.D, 2)
         add("p7", 3, self.D, self.D, 2)
 
     def _bucket_order(self):
@@ -398,7 +439,8 @@ class NativeResNetFPN(object):
 
     def _conv3(self, P, probs, Cout, Cin, flags, klass=48, f24=False, fold=False):
         """probs: [(x, y, mask or None, packed, bias or None)]: independent 3x3 convolutions of one
-        (Cout, Cin) in one launch; f24: truthy = on the F(2x4, 3x3) engine (packs from ssad_conv_wino24_pack_filters),
+        (Cout, Cin) in one launch; f24: True = on the F(2x4, 3x3) engine (packs from ssad_conv_wino24_pack_filters),
+        "direct" = the direct kernel (packs from ssad_conv_pack_filter), False = F(2x2),
         3 = on the split-operand engine (conv3x3_split.hip; its workspace is bound when the program is finished)."""
         if f24 == 3:
             arr = (K.ConvLevel * len(probs))()
@@ -416,6 +458,9 @@ class NativeResNetFPN(object):
                         keep=[t for p in probs for t in p if t is not None])
             self._split_ops.append(idx)
             return
+        direct = f24 == "direct"
+        if direct:
+            klass, f24 = 18, False
         if f24:
             klass = 46 if self.train else 47
         arr = (K.ConvLevel * len(probs))()
@@ -424,7 +469,7 @@ class NativeResNetFPN(object):
                                  x.shape[0], x.shape[2], x.shape[3], packed.data_ptr(),
                                  bias.data_ptr() if bias is not None else 0)
         px = sum(p[0].shape[0] * p[0].shape[2] * p[0].shape[3] for p in probs)
-        P.add(PR.CONV3X3, klass, i=(len(probs), Cout, Cin, flags, 2 if f24 else 1), p=(arr, None, None),
+        P.add(PR.CONV3X3, klass, i=(len(probs), Cout, Cin, flags, 0 if direct else 2 if f24 else 1), p=(arr, None, None),
               work=2.0 * 9 * Cout * Cin * px, keep=[t for p in probs for t in p if t is not None])
 
     def _wgrad3(self, P, x, dy, layer):
@@ -571,6 +616,13 @@ class NativeResNetFPN(object):
         # (default on: step -0.1 ... -1.3 ms in four same-box A/B pairs, profiles/r06_experiments.md)
         use_split = (int(os.environ.get("SSAD_SPLIT_CONV", "511")) & 16) != 0 and (use_f24 or use_f24_train)
         split_frozen, split_train = [], []
+        direct_frozen, direct_train = [], []
+
+        def accepts(floats, l):
+            """Does the engine whose pack-size function is `floats` take this layer's widths (forward, and the
+            data gradient's transposed widths when it is trained)?  A refusal (size 0) sends the layer to the next
+            engine of the chain below, the rule of the split filter gradient (_wgrad3)."""
+            return floats(l.cout, l.cin) > 0 and (not l.train or floats(l.cin, l.cout) > 0)
         self._split_ops, self._split_need = [], 0
         self._gemm_split_ops = []
         self._gemm_split = (int(os.environ.get("SSAD_SPLIT_CONV", "511")) & 128) != 0
@@ -595,20 +647,29 @@ class NativeResNetFPN(object):
                 # gradients read the filter in its natural layout)
                 l.wt = self._t(l.cin * 9, l.cout)
                 trs.append((l.w, l.wt, l.cout, l.cin * 9, l.cout))
-            elif l.k == 3 and use_split and l.cout >= 256 and l.cin >= 256:
+            elif (l.k == 3 and use_split and l.cout >= 256 and l.cin >= 256
+                  and accepts(lib.ssad_conv_split_filter_floats, l)):
                 l.pf = self._t(lib.ssad_conv_split_filter_floats(l.cout, l.cin))
                 l.pd = self._t(lib.ssad_conv_split_filter_floats(l.cin, l.cout)) if l.train else None
                 l.f24 = 3
                 (split_train if l.train else split_frozen).append(l)
-            elif l.k == 3 and use_f24 and not l.train and l.cout >= 128:
+            elif l.k == 3 and use_f24 and not l.train and l.cout >= 128 and accepts(lib.ssad_conv_wino24_filter_floats, l):
                 l.pf = self._t(lib.ssad_conv_wino24_filter_floats(l.cout, l.cin))
                 l.f24 = True
                 wino24_frozen.append(l)
-            elif l.k == 3 and use_f24_train and l.train and l.cout >= 128 and l.cin >= 128:
+            elif (l.k == 3 and use_f24_train and l.train and l.cout >= 128 and l.cin >= 128
+                  and accepts(lib.ssad_conv_wino24_filter_floats, l)):
                 l.pf = self._t(lib.ssad_conv_wino24_filter_floats(l.cout, l.cin))
                 l.pd = self._t(lib.ssad_conv_wino24_filter_floats(l.cin, l.cout))
                 l.f24 = True
                 wino24_train.append(l)
+            elif l.k == 3 and (l.cout < 32 or l.cin < 32 or not accepts(lib.ssad_conv_wino_filter_floats, l)):
+                # narrower than one 32-row tile of the F(2x2) engine (res2 of a quarter-width student, 16 -> 16): the
+                # direct kernel, the subnets' rule for outputs below 32 channels (head_pipeline._use_wino)
+                l.pf = self._t(lib.ssad_conv_packed_filter_floats(l.cout, l.cin))
+                l.pd = self._t(lib.ssad_conv_packed_filter_floats(l.cin, l.cout)) if l.train else None
+                l.f24 = "direct"
+                (direct_train if l.train else direct_frozen).append(l)
             elif l.k == 3:
                 l.pf = self._t(lib.ssad_conv_wino_filter_floats(l.cout, l.cin))
                 need_pd = l.train                  # every trainable 3x3 sends a gradient further down
@@ -654,6 +715,10 @@ class NativeResNetFPN(object):
                 tgt.add(PR.WINO_PACK_FILTERS, 54, i=(len(ls), 3), p=(tab,),
                         work=4.0 * sum(l.w.numel() + l.pf.numel() + (l.pd.numel() if l.pd is not None else 0)
                                        for l in ls))
+        for tgt, ls in ((prep, direct_frozen), (P, direct_train)):
+            for l in ls:
+                tgt.add(PR.PACK_FILTER, 54, i=(l.cout, l.cin), p=(l.w, l.pf, l.pd),
+                        work=4.0 * (l.w.numel() + l.pf.numel() + (l.pd.numel() if l.pd is not None else 0)))
         # the pointwise filters' split copies (which layers need one is known once the passes are emitted: the table is
         # filled in below)
         gp_max = 2 * sum(1 for l in L.values() if l.k == 1)
@@ -708,7 +773,7 @@ class NativeResNetFPN(object):
         st = L["stem.0"]
         oh, ow = H // 2, W // 2
         kk = 3 * 49
-        self.stem_z = self._t(N, 64, oh, ow)
+        self.stem_z = self._t(N, st.cout, oh, ow)
         # stem: 7x7/2 as an implicit GEMM (K = 147 gathered by the DMA: no column buffer -- it was
         # 1.35 GB per 16 images), then bias + ReLU + 3x3/2 max pool in one pass.  Image groups keep
         # every buffer offset below 2 GiB.
@@ -719,8 +784,8 @@ class NativeResNetFPN(object):
             d.P = oh * ow
             P.add(PR.CONV_IMPLICIT, 53, i=(3, H, W, 7, 2, 3), p=(d,), work=2.0 * (n1 - n0) * oh * ow * kk * st.cout,
                   keep=[st.wt, self.image, self.stem_z])
-        c1 = self._t(N, 64, oh // 2, ow // 2)
-        self._ew(P, PR.STEM_POOL, i=(N, 64, oh, ow, 1), p=(self.stem_z, st.b, c1), nbytes=4.0 * 1.25 * self.stem_z.numel())
+        c1 = self._t(N, st.cout, oh // 2, ow // 2)
+        self._ew(P, PR.STEM_POOL, i=(N, st.cout, oh, ow, 1), p=(self.stem_z, st.b, c1), nbytes=4.0 * 1.25 * self.stem_z.numel())
         x = c1
         self.saved = {}
         stage_out = {}
@@ -990,34 +1055,52 @@ class NativeDistillModel(object):
 
     def __init__(self, heads, student_arch="r50", teacher_arch="r101", N=16, image_hw=(640, 896), device="cuda",
                  process_group=None, world_size=1, lr=None, momentum=0.9, weight_decay=1e-4, two_streams=None,
-                 overlap_wgrad=None, student_src=None, teacher_src=None, student_scales=None):
+                 overlap_wgrad=None, student_src=None, teacher_src=None, student_scales=None,
+                 student_channel_ratio=1.0):
         """lr: None = the subnets' learning rate (one schedule for the whole detector,
         optimizer.py:95-130).  two_streams / overlap_wgrad: None = environment
         (SSAD_NATIVE_TWO_STREAMS / SSAD_OVERLAP_WGRAD, default on).  *_src: initial weights
-        (NativeResNetFPN._alloc_params), student_scales: the folded AffineChannel scales."""
+        (NativeResNetFPN._alloc_params), student_scales: the folded AffineChannel scales.
+        student_channel_ratio: RESNETS.CHANNEL_RATIO of the student (a thin student under a full-width teacher:
+        the teacher is built from its own cfg, model_builder.py:384 switch_to_teacher(), ratio 1).  `heads` must have
+        been built for the two widths: HeadConfig.fpn_dim = the student's FPN dimension, teacher_fpn_dim = the
+        teacher's (head_pipeline.DistillHeads)."""
         import os
         self.heads = heads
+        self.student_channel_ratio = float(student_channel_ratio)
         self.has_teacher = teacher_arch not in (None, "none")
         assert self.has_teacher == bool(getattr(heads, "distill", True))
+        if self.has_teacher and getattr(heads, "Dt", 256) != 256:
+            raise K.KernelError("NativeDistillModel: the teacher is full width (FPN dimension 256), its subnets were "
+                                "built for %d" % heads.Dt)
         lr = float(heads.lr.item()) if lr is None else lr
         self.f16 = bool(getattr(heads, "F16", False))
         # fp16 subnets that exchange blocked fp16 tensors with the backbone: the backbones run in the
         # same precision (config 5: every convolution of the net, conv_op_cudnn.cc:631-636)
         self.backbone_f16 = self.f16 and bool(getattr(heads, "blocked_io", False))
+        if self.backbone_f16 and self.student_channel_ratio != 1.0:
+            raise K.KernelError("NativeDistillModel: student_channel_ratio %r with the fp16-storage backbones is not "
+                                "supported (backbone_f16's kernels were written for the full widths)"
+                                % (student_channel_ratio,))
+        want_s = student_widths(student_arch, student_channel_ratio).fpn_dim      # (raises before any allocation)
+        if getattr(heads, "D", want_s) != want_s:
+            raise K.KernelError("NativeDistillModel: the subnets were built for FPN dimension %d, a %s student of "
+                                "channel_ratio %r has %d" % (heads.D, student_arch, student_channel_ratio, want_s))
         kw = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, process_group=process_group,
                   world_size=world_size, affine_scales=student_scales,
                   skip_flag=heads.ls_counters if self.f16 else None, overlap_wgrad=overlap_wgrad)
         if self.backbone_f16:
             from .backbone_f16 import NativeResNetFPNF16
             self.student = NativeResNetFPNF16(
-                student_arch, N, image_hw, device, train=True, src=student_src,
+                student_arch, N, image_hw, device, train=True, src=student_src, channel_ratio=student_channel_ratio,
                 heads_io=dict(fpn_out=heads.in_blk["student"], inv_scale=heads.ls_state[1:2],
                               d_fpn_in=(heads.dbuf["cls"][0], heads.dbuf["bbox"][0])), **kw)
             self.teacher = NativeResNetFPNF16(
                 teacher_arch, N, image_hw, device, train=False, src=teacher_src, process_group=process_group,
                 world_size=world_size, heads_io=dict(fpn_out=heads.in_blk["teacher"])) if self.has_teacher else None
         else:
-            self.student = NativeResNetFPN(student_arch, N, image_hw, device, train=True, src=student_src, **kw)
+            self.student = NativeResNetFPN(student_arch, N, image_hw, device, train=True, src=student_src,
+                                           channel_ratio=student_channel_ratio, **kw)
             self.teacher = NativeResNetFPN(teacher_arch, N, image_hw, device, train=False, src=teacher_src,
                                            process_group=process_group,
                                            world_size=world_size) if self.has_teacher else None

@@ -21,6 +21,7 @@ through the workspace (tests check that), but scheduled MI355X-first:
 
 torch provides device memory, streams and torch.distributed only.
 """
+import dataclasses
 from collections import OrderedDict
 
 import numpy as np
@@ -95,7 +96,11 @@ class DistillHeads(object):
     def __init__(self, cfg=None, N=2, shapes=synth.LEVEL_SHAPES_600, device="cuda",
                  student_init=None, teacher_init=None, teacher_bbox_tower=True,
                  lr=0.01, momentum=0.9, weight_decay=1e-4, process_group=None, world_size=1,
-                 distill=True, overlap_wgrad=None, blocked_io=False):
+                 distill=True, overlap_wgrad=None, blocked_io=False, teacher_fpn_dim=None):
+        """teacher_fpn_dim: FPN dimension of the TEACHER's subnets when it differs from cfg.fpn_dim (the student's):
+        a thin student of RESNETS.CHANNEL_RATIO r has int(FPN.DIM * r) channels on every level while the teacher,
+        built from its own cfg, keeps FPN.DIM.  The two networks' towers then have different (Cout, Cin) and run as
+        separate launches, each under the engine rules of its own width (fp32 pipeline only)."""
         self.cfg = cfg or HeadConfig()
         self.N, self.shapes, self.device = N, list(shapes), device
         self.distill = bool(distill)
@@ -135,8 +140,13 @@ class DistillHeads(object):
         self.dp = BucketedAllReduce(process_group, world_size)
         cfg = self.cfg
         self.A, self.C, self.D = cfg.num_anchors, cfg.num_classes - 1, cfg.fpn_dim
+        self.Dt = int(teacher_fpn_dim) if (teacher_fpn_dim and self.distill) else self.D
+        if self.Dt != self.D and self.F16:
+            raise K.KernelError("DistillHeadsF16: teacher_fpn_dim %d != fpn_dim %d is not supported (the fp16 subnets "
+                                "run teacher and student towers as one launch of one width)" % (self.Dt, self.D))
         self.params = FlatParams(cfg, device, student_init)
-        self.teacher = FlatParams(cfg, device, teacher_init) if self.distill else None
+        t_cfg = cfg if self.Dt == self.D else dataclasses.replace(cfg, fpn_dim=self.Dt)
+        self.teacher = FlatParams(t_cfg, device, teacher_init) if self.distill else None
         self.grads = FlatParams(cfg, device)
         self.moms = FlatParams(cfg, device)
         nlev = len(self.shapes)
@@ -170,7 +180,7 @@ class DistillHeads(object):
         # inputs are bound per step (the FPN tensors belong to the caller); these placeholders
         # give the level tables valid addresses until the first bind
         self.fpn_in = lv(D)
-        self.t_fpn_in = self.fpn_in
+        self.t_fpn_in = self.fpn_in if self.Dt == D else lv(self.Dt)
         self.labels = [torch.zeros((self.N, self.A, h, w), dtype=torch.int32, device=self.device)
                        for (h, w) in self.shapes]
         # student activations (kept for backward) and their gradients
@@ -184,7 +194,8 @@ class DistillHeads(object):
         self.d_fpn = {t: lv(D) for t in ("cls", "bbox")}
         if self.distill:
             # teacher scratch: two ping-pong feature sets per tower + probabilities
-            self.t_buf = {"cls": [lv(D), lv(D)], "bbox": [lv(D), lv(D)]}
+            Dt = self.Dt
+            self.t_buf = {"cls": [lv(Dt), lv(Dt)], "bbox": [lv(Dt), lv(Dt)]}
             self.t_prob = lv(self.A * self.C)
             self.t_bbox = lv(4 * self.A) if self.teacher_bbox_tower else None
 
@@ -497,6 +508,27 @@ class DistillHeads(object):
                 probs.append((sx[t], out, None, self.packed[name][0], self.params[name + "_b"]))
                 who.append("student")
                 sx[t] = out
+            if self.Dt != D:
+                # a thin student under a full-width teacher: two widths, two launches per depth, each on the engine the
+                # rules below give a launch of its width (split-operand, else F(2x4) from 128 outputs, else F(2x2))
+                for w, dim in (("teacher", self.Dt), ("student", D)):
+                    plist = [p for p, ww in zip(probs, who) if ww == w]
+                    if not plist:
+                        continue
+                    name = self._layers("cls")[i]
+                    if self.split_conv & 4:
+                        _, arr = self._emit_conv(P, plist, dim, dim, K.CONV_RELU, 28, split=True)
+                    elif self._f24_use(w, name, dim, dim, "fwd"):
+                        _, arr = self._emit_conv(P, plist, dim, dim, K.CONV_RELU, 21 if w == "teacher" else 23, f24=True)
+                    else:
+                        _, arr = self._emit_conv(P, plist, dim, dim, K.CONV_RELU, 2)
+                    if i == 0:
+                        k = 0
+                        for (xs, _, _, _, _) in plist:
+                            for l in range(len(xs)):
+                                self._in_slots.append((arr, k, w, l))
+                                k += 1
+                continue
             if self.split_conv & 4:
                 # every tower of this depth on the split-operand engine, one launch (class 28)
                 _, arr = self._emit_conv(P, probs, D, D, K.CONV_RELU, 28, split=True)
@@ -545,12 +577,15 @@ class DistillHeads(object):
         if self.distill:
             f24 = self._f24_layer(cp, AC)
             self._emit_conv(P, [(tx["cls"], self.t_prob, None, self.t_packed_for(cp), self.teacher[cp + "_b"])],
-                            AC, D, K.CONV_SIGMOID, 25 if sp else 20 if f24 else 3, f24=f24, split=sp)
+                            AC, self.Dt, K.CONV_SIGMOID, 25 if sp else 20 if f24 else 3, f24=f24, split=sp)
         f24 = self._f24_use("student", cp, AC, D, "fwd")
         self._emit_conv(P, [(sx["cls"], self.cls_logits, None, self.packed[cp][0], self.params[cp + "_b"])],
                         AC, D, 0, 26 if sp else 22 if f24 else 3, f24=f24, split=sp)
         probs = [(sx["bbox"], self.bbox_pred, None, self.packed[bp][0], self.params[bp + "_b"])]
-        if self.teacher_bbox_tower:
+        if self.teacher_bbox_tower and self.Dt != D:
+            self._emit_conv(P, [(tx["bbox"], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"])],
+                            A4, self.Dt, 0, 4)
+        elif self.teacher_bbox_tower:
             probs.append((tx["bbox"], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"]))
         self._emit_conv(P, probs, A4, D, 0, 4)
 
@@ -702,7 +737,8 @@ class DistillHeads(object):
             for x in list(s) + list(t if self.distill else []):
                 if x.dtype != torch.float32 or not x.is_contiguous() or x.device.type != dev_type:
                     raise K.KernelError("FPN levels must be contiguous float32 tensors on %s" % dev_type)
-            if any(tuple(a.shape) != tuple(b.shape) for a, b in zip(s, self.fpn_in)):
+            if any(tuple(a.shape) != tuple(b.shape) for a, b in zip(s, self.fpn_in)) or (
+                    self.distill and any(tuple(a.shape) != tuple(b.shape) for a, b in zip(t, self.t_fpn_in))):
                 raise K.KernelError("FPN levels do not match the shapes this pipeline was built for")
             self._rebind_inputs(s, t)
             self.fpn_in, self.t_fpn_in = s, t

@@ -6,9 +6,11 @@ conv, in-place Relu / Sum, StopGradient after res2 = TRAIN.FREEZE_AT 2) and
 FPN.py:116-250 (lateral 1x1 on res5/res4/res3, UpsampleNearest + Sum top-down path,
 3x3 output convs, extra stride-2 levels P6 from res5 and P7 from relu(P6)).
 Checked against a capture of the reference builder (tests/golden/
-backbone_graph_r50_fpn.json).  Every op runs on this repo's HIP operator surface:
+backbone_graph_r50_fpn.json; backbone_graph_r50_fpn_ratio{50,25}.json for the thin students of
+RESNETS.CHANNEL_RATIO, ResNet.py:99-124 and FPN.py:122,501).  Every op runs on this repo's HIP operator surface:
 3x3/s1 convolutions on the matrix-core engine, the other geometries on the default
 im2col + GEMM engine."""
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 from ..caffe2_hip import core
@@ -20,6 +22,36 @@ def const_fill(v):
     return ("ConstantFill", {"value": v})
 
 
+class ChannelRatioError(ValueError):
+    """RESNETS.CHANNEL_RATIO outside what this repo builds (see channel_widths)."""
+
+
+# stem, bottleneck inner width per stage (res2..res5), stage outputs (res2..res5), FPN dimension
+Widths = namedtuple("Widths", "stem inner stage fpn_dim")
+
+WIDTH_MULTIPLE = 16         # every derived width: a positive multiple of this (0.25, 0.5, 0.75, 1.0 for R-50 / R-101)
+
+
+def channel_widths(channel_ratio=1.0, num_groups=1, width_per_group=64, fpn_dim=256, check=True):
+    """The reference's width arithmetic for a student of RESNETS.CHANNEL_RATIO = r; Python's int() truncates:
+    stem 64, not scaled (ResNet.py:94-98); inner width int(NUM_GROUPS * WIDTH_PER_GROUP * r) * 2**stage_index
+    (ResNet.py:99: truncated ONCE, then doubled); stage outputs int(256 r) .. int(2048 r) (ResNet.py:102-118,
+    FPN.py:501); FPN dimension int(FPN.DIM * r) (FPN.py:122), which the RetinaNet subnets inherit as dim_in.
+    check: raise ChannelRatioError unless 0 < r <= 1 and every width is a positive multiple of 16."""
+    r = float(channel_ratio)
+    inner0 = int(num_groups * width_per_group * r)
+    w = Widths(64, tuple(inner0 * 2 ** i for i in range(4)), tuple(int(c * r) for c in (256, 512, 1024, 2048)),
+               int(fpn_dim * r))
+    if check:
+        every = w.inner + w.stage + (w.fpn_dim,)
+        if not (0.0 < r <= 1.0) or any(c <= 0 or c % WIDTH_MULTIPLE for c in every):
+            raise ChannelRatioError(
+                "channel_ratio %r: every derived width must be a positive multiple of %d and the ratio at most 1 "
+                "(0.25, 0.5, 0.75, 1.0); got inner %s, stages %s, FPN %d" % (channel_ratio, WIDTH_MULTIPLE,
+                                                                            list(w.inner), list(w.stage), w.fpn_dim))
+    return w
+
+
 @dataclass
 class BodyConfig:
     block_counts: tuple = (3, 4, 6, 3)        # ResNet-50; ResNet-101: (3, 4, 23, 3)
@@ -27,10 +59,14 @@ class BodyConfig:
     stride_1x1: bool = True                   # RESNETS.STRIDE_1X1
     num_groups: int = 1                       # RESNETS.NUM_GROUPS (ResNeXt: 64)
     width_per_group: int = 64                 # RESNETS.WIDTH_PER_GROUP (ResNeXt-101-64x4d: 4)
-    fpn_dim: int = 256                        # FPN.DIM
+    fpn_dim: int = 256                        # FPN.DIM (before the ratio: the body builds int(fpn_dim * channel_ratio))
+    channel_ratio: float = 1.0                # RESNETS.CHANNEL_RATIO (ResNet.py:99-124, FPN.py:122,501)
     k_min: int = 3                            # FPN.RPN_MIN_LEVEL
     k_max: int = 7                            # FPN.RPN_MAX_LEVEL
     use_cudnn_engine: bool = True             # keep the reference's engine="CUDNN" argument
+
+    def widths(self, check=True):
+        return channel_widths(self.channel_ratio, self.num_groups, self.width_per_group, self.fpn_dim, check)
 
 
 @dataclass
@@ -119,7 +155,11 @@ def add_shortcut(model, prefix, blob_in, dim_in, dim_out, stride):
 
 def add_residual_block(model, prefix, blob_in, dim_in, dim_out, dim_inner, dilation,
                        stride_init=2, inplace_sum=False):
-    """ResNet.py:158-197."""
+    """ResNet.py:158-197.  The reference recognises the first stage by dim_in == 64 (the stem's width).  A student of
+    RESNETS.CHANNEL_RATIO = 0.25 has int(256 * 0.25) = 64 channels leaving res2 as well, so the reference gives
+    res3_0 stride 1 too (and res2_0 no projection shortcut): its res3..res5 then sit at strides 4, 8, 16 while its
+    anchors stay at 8..128.  This builder restates that (it is what the capture shows); the native backbone strides
+    by stage index (backbone_pipeline.NativeResNetFPN)."""
     stride = stride_init if (dim_in != dim_out and dim_in != 64 and dilation == 1) else 1
     tr = bottleneck_transformation(model, blob_in, dim_in, dim_out, stride, prefix, dim_inner,
                                    group=model.cfg.num_groups, dilation=dilation)
@@ -144,22 +184,24 @@ def add_resnet_conv5_body(model):
     p = model.AffineChannel(p, "res_conv1_bn", dim=64, inplace=True)
     p = model.Relu(p, p)
     p = model.MaxPool(p, "pool1", kernel=3, pad=1, stride=2)
-    dim_in, dim_bottleneck = 64, cfg.num_groups * cfg.width_per_group      # ResNet.py:99
+    wd = cfg.widths()
+    dim_in, dim_bottleneck = wd.stem, wd.inner[0]                          # ResNet.py:99
+    o2, o3, o4, o5 = wd.stage
     n1, n2, n3, n4 = cfg.block_counts
     stage_out = {}
-    s, dim_in = add_stage(model, "res2", p, n1, dim_in, 256, dim_bottleneck, 1)
+    s, dim_in = add_stage(model, "res2", p, n1, dim_in, o2, dim_bottleneck, 1)
     if cfg.freeze_at == 2:
         model.StopGradient(s, s)
     stage_out[2] = (s, dim_in)
-    s, dim_in = add_stage(model, "res3", s, n2, dim_in, 512, dim_bottleneck * 2, 1)
+    s, dim_in = add_stage(model, "res3", s, n2, dim_in, o3, dim_bottleneck * 2, 1)
     if cfg.freeze_at == 3:
         model.StopGradient(s, s)
     stage_out[3] = (s, dim_in)
-    s, dim_in = add_stage(model, "res4", s, n3, dim_in, 1024, dim_bottleneck * 4, 1)
+    s, dim_in = add_stage(model, "res4", s, n3, dim_in, o4, dim_bottleneck * 4, 1)
     if cfg.freeze_at == 4:
         model.StopGradient(s, s)
     stage_out[4] = (s, dim_in)
-    s, dim_in = add_stage(model, "res5", s, n4, dim_in, 2048, dim_bottleneck * 8, 1)
+    s, dim_in = add_stage(model, "res5", s, n4, dim_in, o5, dim_bottleneck * 8, 1)
     if cfg.freeze_at == 5:
         model.StopGradient(s, s)
     stage_out[5] = (s, dim_in)
@@ -186,7 +228,7 @@ def add_fpn_resnet_conv5_body(model):
     lateral_in = [stages[l][0] for l in levels]
     dims = [stages[l][1] for l in levels]
     out_blobs = ["fpn_inner_%s" % b for b in lateral_in]
-    fpn_dim = cfg.fpn_dim
+    fpn_dim = cfg.widths().fpn_dim                                         # FPN.py:122
     model.Conv(lateral_in[0], out_blobs[0], dim_in=dims[0], dim_out=fpn_dim, kernel=1, pad=0,
                stride=1, weight_init=XAVIER, bias_init=const_fill(0.0))
     for i in range(len(levels) - 1):

@@ -46,6 +46,12 @@ class HeadConfig:
     fuse_relu: bool = False               # extension: fold Relu into the conv
     softmax: bool = False                 # RETINANET.SOFTMAX: softmax head over num_classes (background kept)
 
+    @classmethod
+    def for_body(cls, body_cfg, **kw):
+        """The subnets of a body built from `body_cfg` (modeling.resnet_fpn.BodyConfig): their width is the dim the
+        FPN builder returns, int(FPN.DIM * RESNETS.CHANNEL_RATIO) (FPN.py:122 -> retinanet_heads.py:63 dim_in)."""
+        return cls(fpn_dim=body_cfg.widths().fpn_dim, k_min=body_cfg.k_min, k_max=body_cfg.k_max, **kw)
+
     @property
     def num_anchors(self):
         return len(self.aspect_ratios) * self.scales_per_octave
@@ -122,10 +128,13 @@ GAUSS = ("GaussianFill", {"std": 0.01})
 ZERO = ("ConstantFill", {"value": 0.0})
 
 
-def add_fpn_retinanet_outputs(model, blobs_in, dim_in, prefix=""):
+def add_fpn_retinanet_outputs(model, blobs_in, dim_in=None, prefix=""):
     """blobs_in: FPN feature blobs ordered coarsest level first (k_max..k_min),
-    as the FPN body returns them.  Returns {level: (cls_pred, bbox_pred)}."""
+    as the FPN body returns them; dim_in: the dim the body returned with them (None: cfg.fpn_dim, see
+    HeadConfig.for_body).  Returns {level: (cls_pred, bbox_pred)}."""
     cfg = model.cfg
+    if dim_in is None:
+        dim_in = cfg.fpn_dim
     assert len(blobs_in) == cfg.k_max - cfg.k_min + 1
     A = cfg.num_anchors
     cls_pred_dim = cfg.num_classes if cfg.softmax else cfg.num_classes - 1      # retinanet_heads.py:78-80

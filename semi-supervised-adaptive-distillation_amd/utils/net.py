@@ -24,6 +24,11 @@ ResNet.py / FPN.py (captured from the imported reference builder in
 tests/golden/backbone_graph_*.json): conv1_w + res_conv1_bn_*, res{2..5}_{i}_branch2{a,b,c}_*,
 res{N}_{0}_branch1_* (projection), fpn_inner_res5_{n}_sum_*, fpn_inner_res{4,3}_{n}_sum_lateral_*,
 fpn_res{5,4,3}_{n}_sum_*, fpn_6_*, fpn_7_*; the teacher's under `teacher/` (net.py:71-78).
+
+Thin students (RESNETS.CHANNEL_RATIO, `channel_ratio=`): the same blobs at the scaled dims (captures:
+tests/golden/thin_graph_r50_fpn_ratio*.json); at ratio 0.25 res2 leaves int(256 * 0.25) = 64 channels, the
+stem's width, so `res2_0_branch1_*` does not exist (ResNet.py:200-202).  A file written for another ratio is
+refused as a whole (WeightsWidthError) instead of being skipped blob by blob.
 """
 import logging
 import os
@@ -229,7 +234,36 @@ def save_model_to_weights_file(weights_file, store, cfg_yaml=""):
 _BLOCKS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3)}
 
 
-def backbone_blob_names(arch):
+class WeightsWidthError(ValueError):
+    """A weights file whose backbone was built with another RESNETS.CHANNEL_RATIO than the network it is loaded
+    into: states the file's and the network's shape of the first filter that differs."""
+
+
+def check_backbone_widths(blobs, arch, channel_ratio=1.0, prefix=""):
+    """Raise WeightsWidthError when the filters `blobs` holds for this backbone are those of another width: every
+    width-scaled filter present (all but the stem, which no ratio scales) has another shape than the network of
+    `channel_ratio`.  One odd blob among matching ones is not that: it is reported and skipped by the loaders as the
+    reference does (net.py:106-119)."""
+    from ..backbone_pipeline import NativeResNetFPN
+    shapes = NativeResNetFPN.layer_shapes(arch, channel_ratio)
+    names = backbone_blob_names(arch, channel_ratio)
+    seen, bad = 0, []
+    for layer, (wn, _, _) in names.items():
+        if layer == "stem.0" or prefix + wn not in blobs:
+            continue
+        seen += 1
+        have = tuple(np.asarray(blobs[prefix + wn]).shape)
+        if have != shapes[layer]:
+            bad.append((prefix + wn, have, shapes[layer]))
+    if seen and len(bad) == seen:
+        n, have, want = bad[0]
+        raise WeightsWidthError(
+            "the weights file was written for another channel ratio than %r: %s has shape %s in the file, the %s "
+            "network of that ratio has %s (and so for all %d filters of the body and FPN present)"
+            % (channel_ratio, n, have, arch, want, seen))
+
+
+def backbone_blob_names(arch, channel_ratio=1.0):
     """Native layer name -> (filter blob, AffineChannel scale blob or None, bias blob): the
     reference's names for every convolution of a ResNet / ResNeXt-FPN RetinaNet body
     (ResNet.py:85-130,221-283 add_stage / bottleneck_transformation / basic_bn_shortcut /
@@ -247,7 +281,9 @@ def backbone_blob_names(arch):
             for part, br in (("c1", "branch2a"), ("c2", "branch2b"), ("c3", "branch2c")):
                 b = "%s_%s" % (pre, br)
                 names["res%d.%d.%s" % (stage, j, part)] = (b + "_w", b + "_bn_s", b + "_bn_b")
-            if j == 0:          # the stage's first block changes width (and stride): projection shortcut
+            # the stage's first block changes width (and stride): projection shortcut -- but for res2_0 of a
+            # quarter-width student, 64 -> int(256 * 0.25) = 64 (ResNet.py:200-202: dim_in == dim_out, no branch1)
+            if j == 0 and not (stage == 2 and int(256 * float(channel_ratio)) == 64):
                 b = pre + "_branch1"
                 names["res%d.%d.proj" % (stage, j)] = (b + "_w", b + "_bn_s", b + "_bn_b")
     last = {stage: "res%d_%d_sum" % (stage, blocks[stage - 2] - 1) for stage in (3, 4, 5)}
@@ -260,15 +296,17 @@ def backbone_blob_names(arch):
     return names
 
 
-def backbone_from_blobs(blobs, arch, prefix="", strict=True):
+def backbone_from_blobs(blobs, arch, prefix="", strict=True, channel_ratio=1.0):
     """Fold a Detectron blob dict into what NativeResNetFPN(src=, affine_scales=) takes.
     -> (state {layer.weight / layer.bias: float32 tensor}, scales {layer: [cout] float32 tensor},
         momentum {layer.weight / layer.bias: tensor} for the blobs that carry `_momentum`,
         missing [blob names])
     strict: a missing blob raises KeyError (a backbone with holes computes garbage); otherwise the
-    layer is left out of `state` and reported."""
+    layer is left out of `state` and reported.  channel_ratio: the width of the network the blobs are meant for; a
+    file of another width raises WeightsWidthError (check_backbone_widths)."""
+    check_backbone_widths(blobs, arch, channel_ratio, prefix)
     state, scales, moms, missing = {}, {}, {}, []
-    for layer, (wn, sn, bn) in backbone_blob_names(arch).items():
+    for layer, (wn, sn, bn) in backbone_blob_names(arch, channel_ratio).items():
         need = [n for n in (wn, sn, bn) if n is not None]
         absent = [prefix + n for n in need if prefix + n not in blobs]
         if absent:
@@ -311,10 +349,11 @@ def load_backbone(net, blobs, prefix="", load_momentum=True, strict=False):
     `net.missing_blobs`.  strict=True raises KeyError / ValueError instead (a body with holes computes
     garbage unless the caller meant it: the reference's standard TRAIN.WEIGHTS is an ImageNet body that
     holds no fpn_* blob)."""
-    state, scales, moms, missing = backbone_from_blobs(blobs, net.arch, prefix, strict=strict)
+    ratio = getattr(net, "channel_ratio", 1.0)
+    state, scales, moms, missing = backbone_from_blobs(blobs, net.arch, prefix, strict=strict, channel_ratio=ratio)
     for n in missing:
         logger.info("%s not found", n)
-    names = backbone_blob_names(net.arch)
+    names = backbone_blob_names(net.arch, ratio)
     for name, layer in net._layers.items():
         if name + ".weight" not in state:
             continue
@@ -352,7 +391,7 @@ def backbone_to_blobs(net, prefix="", momentum=True):
     and the FPN's filters and biases; net.py:137-168)."""
     out = OrderedDict()
     aff = getattr(net, "affine_scale_values", {})
-    for name, (wn, sn, bn) in backbone_blob_names(net.arch).items():
+    for name, (wn, sn, bn) in backbone_blob_names(net.arch, getattr(net, "channel_ratio", 1.0)).items():
         layer = net._layers[name]
         w = layer.w.detach().float().cpu()
         b = layer.b.detach().float().cpu()
@@ -390,7 +429,8 @@ def native_model_from_weights_files(heads, weights_file, teacher_weights_file=No
     `weights_file` (student; its `teacher/` blobs or `teacher_weights_file` for the teacher:
     net.py:71-78), momentum included.  Blobs the file lacks keep the model's initialisation and are
     returned in `missing`, as the reference does (an ImageNet body-only R-50.pkl is the standard
-    TRAIN.WEIGHTS); strict=True raises on the first hole.  -> (model, loaded names, missing names)"""
+    TRAIN.WEIGHTS); strict=True raises on the first hole.  model_kw: NativeDistillModel's, student_channel_ratio
+    among them (a file of another width raises WeightsWidthError).  -> (model, loaded names, missing names)"""
     from ..backbone_pipeline import NativeDistillModel
     src, _ = _blobs_and_cfg(load_object(weights_file))
     src = dict(src)
@@ -398,7 +438,8 @@ def native_model_from_weights_files(heads, weights_file, teacher_weights_file=No
         tsrc, _ = _blobs_and_cfg(load_object(teacher_weights_file))
         for k, v in tsrc.items():
             src["teacher/" + k] = v
-    s_state, s_scales, _, _ = backbone_from_blobs(src, student_arch, strict=strict)
+    s_state, s_scales, _, _ = backbone_from_blobs(src, student_arch, strict=strict,
+                                                  channel_ratio=model_kw.get("student_channel_ratio", 1.0))
     has_teacher = teacher_arch not in (None, "none")
     t_state = t_scales = None
     if has_teacher:
@@ -418,7 +459,7 @@ def initialize_from_blobs(model, src, strict=False):
         load_backbone(net, src, prefix, load_momentum=not prefix, strict=strict)
         gone = set(net.missing_blobs)
         missing += net.missing_blobs
-        loaded += [prefix + n for t in backbone_blob_names(net.arch).values() for n in t
+        loaded += [prefix + n for t in backbone_blob_names(net.arch, getattr(net, "channel_ratio", 1.0)).values() for n in t
                    if n is not None and prefix + n not in gone]
     owned = set(loaded) | set(n + "_momentum" for n in loaded)
     for k in list(model.heads.preserved):
