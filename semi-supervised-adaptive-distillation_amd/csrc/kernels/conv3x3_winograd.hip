@@ -371,7 +371,11 @@ __global__ __launch_bounds__(kBlock, 1) void wino_conv_z_kernel(const WArgs args
   unsigned dma_dst = 0;
   auto dma_begin = [&](bool real) {
     dma_real = real;
-    if (real && ld_ch == 0) {
+    // The offsets of a tile serve every chunk (the chunk is the scalar offset) -- except the chunk that holds the
+    // channel tail of K % KC != 0: its slots for channels >= K get the out-of-range offset (zeros), not the next
+    // image's channels times the pack's zero padding, which is a NaN as soon as that neighbour is Inf or NaN.
+    const int c0 = (ld_ch + t_c0) * KC;
+    if (real && (ld_ch == 0 || c0 + KC > K)) {
       const WTile Tt = get_tile(ld_tile);
       const WLevel& L = args.lv[Tt.l];
       const int H = L.H, W = L.W, HW = H * W;
@@ -388,7 +392,8 @@ __global__ __launch_bounds__(kBlock, 1) void wino_conv_z_kernel(const WArgs args
         const int sb = PAIRS && q >= SP + 2 ? 1 : 0;
         const int gy = (sb ? Tt.y0[1] : Tt.y0[0]) - 1 + r, gx = (sb ? Tt.x0[1] : Tt.x0[0]) - 1 + q - sb * (SP + 2);
         const int n = sb ? Tt.n[1] : Tt.n[0];
-        const bool ok = (e < ZRAW) & (PAIRS || q < PC + 2) & ((unsigned)gy < (unsigned)H) & ((unsigned)gx < (unsigned)W);
+        const bool ok = (e < ZRAW) & (PAIRS || q < PC + 2) & ((unsigned)gy < (unsigned)H) & ((unsigned)gx < (unsigned)W) &
+                        (c0 + 2 * p + hi < K);
         myvoff[j * 64] = ok ? (unsigned)(((n * K + 2 * p + hi) * HW + gy * W + gx) * 4) : kOOBOff;
       }
     }

@@ -343,6 +343,19 @@ def _workspace(nbytes, tag):
     return buf
 
 
+def _own_workspace(workspace, need):
+    """workspace of a launcher that does not use the cache: None (a fresh buffer), a uint8 device tensor (replaced by
+    a fresh buffer when too small) or a callable nbytes -> tensor, whose result is used as it is."""
+    if callable(workspace):
+        workspace = workspace(need)
+        if workspace is None or workspace.numel() < need:
+            raise KernelError("the workspace provider returned less than the %d bytes asked for" % need)
+        return workspace
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device="cuda")
+    return workspace
+
+
 # ---------------------------------------------------------------------------
 # losses
 # ---------------------------------------------------------------------------
@@ -368,12 +381,13 @@ def _distill_levels(levels, outs):
 
 
 def distill_loss_forward(levels, normalizer, *, gamma=1.0, alpha=0.25, beta=0.0,
-                         num_classes=80, ignored_label=-1, scale=1.0):
+                         num_classes=80, ignored_label=-1, scale=1.0, out=None):
     """levels: list of (logits NxDxHxW, teacher_prob, labels NxAxHxW int32).
     Returns a float32 tensor [n_levels] of scalar losses."""
     L = lib()
     n = len(levels)
-    out = torch.empty(n, dtype=torch.float32, device="cuda")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
     outs = [out[i:i + 1] for i in range(n)]
     arr = _distill_levels(levels, outs)
     P = DistillParams(gamma, alpha, beta, num_classes, ignored_label, scale)
@@ -400,11 +414,12 @@ def distill_loss_backward(levels, normalizer, dloss, *, gamma=1.0, alpha=0.25,
     return outs
 
 
-def focal_loss_forward(levels, fg_num, *, gamma=1.0, alpha=0.25, num_classes=80, scale=1.0):
+def focal_loss_forward(levels, fg_num, *, gamma=1.0, alpha=0.25, num_classes=80, scale=1.0, out=None):
     """SigmoidFocalLoss; levels: list of (logits, labels).  Returns [n_levels] losses."""
     L = lib()
     n = len(levels)
-    out = torch.empty(n, dtype=torch.float32, device="cuda")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
     arr = _distill_levels([(x, None, g) for x, g in levels], [out[i:i + 1] for i in range(n)])
     P = FocalParams(gamma, alpha, num_classes, scale)
     nb = L.ssad_distill_loss_workspace_bytes(n)
@@ -484,12 +499,14 @@ def _softmax_focal_levels(levels, probs, outs, need_logits):
     return arr
 
 
-def softmax_focal_loss_forward(levels, fg_num, *, gamma=1.0, alpha=0.25, num_classes=81, scale=1.0, probs=None):
+def softmax_focal_loss_forward(levels, fg_num, *, gamma=1.0, alpha=0.25, num_classes=81, scale=1.0, probs=None,
+                               out=None):
     """SoftmaxFocalLoss; levels: list of (logits [N, A*num_classes, H, W], labels [N, A, H, W] int32);
     num_classes counts the background.  Returns ([n_levels] losses, list of probabilities)."""
     L = lib()
     n = len(levels)
-    out = torch.empty(n, dtype=torch.float32, device="cuda")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
     if probs is None:
         probs = [torch.empty_like(x) for x, _ in levels]
     arr = _softmax_focal_levels(levels, probs, [out[i:i + 1] for i in range(n)], True)
@@ -516,13 +533,13 @@ def softmax_focal_loss_backward(levels, probs, fg_num, dloss, *, gamma=1.0, alph
     return outs
 
 
-def cls_losses_fused(levels, normalizer, fg_num, distill_kw, focal_kw, out=None):
+def cls_losses_fused(levels, normalizer, fg_num, distill_kw, focal_kw, out=None, losses=None):
     """One pass over the logits: returns (distill_losses, focal_losses, dX list) where
-    dX = d(distill)/dx + d(focal)/dx for loss gradients of 1.0."""
+    dX = d(distill)/dx + d(focal)/dx for loss gradients of 1.0.  losses: (distill, focal) float32 [n_levels] to fill."""
     L = lib()
     n = len(levels)
-    dl = torch.empty(n, dtype=torch.float32, device="cuda")
-    fl = torch.empty(n, dtype=torch.float32, device="cuda")
+    dl, fl = losses if losses is not None else (torch.empty(n, dtype=torch.float32, device="cuda"),
+                                                torch.empty(n, dtype=torch.float32, device="cuda"))
     outs = out if out is not None else [torch.empty_like(x) for x, _, _ in levels]
     arr = _distill_levels(levels, outs)
     DP = DistillParams(distill_kw["gamma"], distill_kw["alpha"], distill_kw.get("beta", 0.0),
@@ -606,14 +623,15 @@ def select_smooth_l1_backward(Y_hat, Y, Lc, S, dloss, *, beta=1.0, scale=1.0, ou
     return dy
 
 
-def pow_sum(inputs, power=1.0):
+def pow_sum(inputs, power=1.0, out=None):
     L = lib()
     n = len(inputs)
     for t in inputs:
         _f32c(t, "PowSum input")
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in inputs])
     sizes = (C.c_int64 * n)(*[t.numel() for t in inputs])
-    out = torch.empty((), dtype=torch.float32, device="cuda")
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device="cuda")
     nb = L.ssad_pow_sum_workspace_bytes(n)
     ws = _workspace(nb, "powsum")
     _check(L.ssad_pow_sum(ptrs, sizes, n, power, _ptr(out), _ptr(ws), nb, _stream()),
@@ -630,8 +648,8 @@ def relu_(x):
     return x
 
 
-def relu(x):
-    y = torch.empty_like(x)
+def relu(x, out=None):
+    y = out if out is not None else torch.empty_like(x)
     _check(lib().ssad_relu(_ptr(_f32c(x, "x")), _ptr(y), x.numel(), _stream()), "relu")
     return y
 
@@ -674,14 +692,17 @@ def conv1x1_bias_act2(x1, x2, w12, bias=None, relu=True):
     return y
 
 
-def relu_grad_rowsum(y, dy, want_dx=True):
+def relu_grad_rowsum(y, dy, want_dx=True, out=None):
     """(dx, rowsum[N][C]): dx = y > 0 ? dy : 0 (y None: dx = dy itself) and the plane sums of dx
-    in the same pass; a bias gradient is rowsum.sum(0)."""
+    in the same pass; a bias gradient is rowsum.sum(0).  out: (dx or None, rowsum) to fill."""
     _f32c(dy, "dy")
     N, Cc = dy.shape[0], dy.shape[1]
     hw = dy.numel() // max(N * Cc, 1)
-    dx = torch.empty_like(dy) if (y is not None and want_dx) else None
-    rs = torch.empty((N, Cc), dtype=torch.float32, device="cuda")
+    if out is not None:
+        dx, rs = out
+    else:
+        dx = torch.empty_like(dy) if (y is not None and want_dx) else None
+        rs = torch.empty((N, Cc), dtype=torch.float32, device="cuda")
     _check(lib().ssad_relu_grad_rowsum(_ptr(_f32c(y, "y")) if y is not None else _ptr(None), _ptr(dy),
                                        _ptr(dx), _ptr(rs), N, Cc, hw, _stream()), "relu_grad_rowsum")
     return (dx if y is not None else dy), rs
@@ -714,11 +735,12 @@ def upsample_nearest(x, scale=2, addend=None, out=None):
     return y
 
 
-def max_pool3x3s2_bias_relu(x, bias=None, relu=True):
+def max_pool3x3s2_bias_relu(x, bias=None, relu=True, out=None):
     """relu(maxpool3x3/2,pad1(x) + bias[c]) in one pass (the ResNet stem's tail)."""
     _f32c(x, "x")
     N, Cc, H, W = x.shape
-    y = torch.empty((N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device="cuda")
+    y = out if out is not None else torch.empty((N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32,
+                                                device="cuda")
     if bias is not None:
         _f32c(bias, "bias")
     _check(lib().ssad_max_pool3x3s2_bias_relu(_ptr(x), _ptr(bias), N, Cc, H, W, int(relu), _ptr(y),
@@ -726,10 +748,11 @@ def max_pool3x3s2_bias_relu(x, bias=None, relu=True):
     return y
 
 
-def upsample_nearest_grad(dy, scale=2):
+def upsample_nearest_grad(dy, scale=2, out=None):
     _f32c(dy, "dy")
     N, Cc, OH, OW = dy.shape
-    dx = torch.empty((N, Cc, OH // scale, OW // scale), dtype=torch.float32, device="cuda")
+    dx = out if out is not None else torch.empty((N, Cc, OH // scale, OW // scale), dtype=torch.float32,
+                                                 device="cuda")
     _check(lib().ssad_upsample_nearest_grad(_ptr(dy), _ptr(dx), N, Cc, OH // scale, OW // scale,
                                             scale, _stream()), "upsample_nearest_grad")
     return dx
@@ -765,7 +788,7 @@ def momentum_sgd_update_(w, g, m, lr, momentum=0.9, weight_decay=1e-4, is_bias=F
 # conv 3x3
 # ---------------------------------------------------------------------------
 
-def conv_pack_filter(w, want_fwd=True, want_dgrad=True):
+def conv_pack_filter(w, want_fwd=True, want_dgrad=True, out=None):
     """w: Cout x Cin x 3 x 3.  Returns (packed_fwd, packed_dgrad)."""
     L = lib()
     _f32c(w, "filter")
@@ -773,15 +796,17 @@ def conv_pack_filter(w, want_fwd=True, want_dgrad=True):
     if (kh, kw) != (3, 3):
         raise KernelError("only 3x3 filters")
     pf = torch.empty(L.ssad_conv_packed_filter_floats(Cout, Cin), dtype=torch.float32,
-                     device="cuda") if want_fwd else None
+                     device="cuda") if want_fwd and out is None else None
     pd = torch.empty(L.ssad_conv_packed_filter_floats(Cin, Cout), dtype=torch.float32,
-                     device="cuda") if want_dgrad else None
+                     device="cuda") if want_dgrad and out is None else None
+    if out is not None:         # (packed_fwd, packed_dgrad) to fill, either may be None; decides instead of want_*
+        pf, pd = out
     _check(L.ssad_conv_pack_filter(_ptr(w), Cout, Cin, _ptr(pf), _ptr(pd), _stream()),
            "conv_pack_filter")
     return pf, pd
 
 
-def conv_wino_pack_filter(w, want_fwd=True, want_dgrad=True):
+def conv_wino_pack_filter(w, want_fwd=True, want_dgrad=True, out=None):
     """Winograd-domain filters U = G g G^T in MFMA operand order: (fwd, dgrad)."""
     L = lib()
     _f32c(w, "filter")
@@ -789,15 +814,17 @@ def conv_wino_pack_filter(w, want_fwd=True, want_dgrad=True):
     if (kh, kw) != (3, 3):
         raise KernelError("only 3x3 filters")
     pf = torch.empty(L.ssad_conv_wino_filter_floats(Cout, Cin), dtype=torch.float32,
-                     device="cuda") if want_fwd else None
+                     device="cuda") if want_fwd and out is None else None
     pd = torch.empty(L.ssad_conv_wino_filter_floats(Cin, Cout), dtype=torch.float32,
-                     device="cuda") if want_dgrad else None
+                     device="cuda") if want_dgrad and out is None else None
+    if out is not None:         # (packed_fwd, packed_dgrad) to fill, either may be None; decides instead of want_*
+        pf, pd = out
     _check(L.ssad_conv_wino_pack_filter(_ptr(w), Cout, Cin, _ptr(pf), _ptr(pd), _stream()),
            "conv_wino_pack_filter")
     return pf, pd
 
 
-def conv_wino24_pack_filter(w, want_dgrad=False):
+def conv_wino24_pack_filter(w, want_dgrad=False, out=None):
     """F(2x4, 3x3) filter pack U = G2 g G4^T; want_dgrad: -> (forward, data-gradient) packs (the latter of the
     flipped, transposed filter, Cin x Cout)."""
     L = lib()
@@ -805,15 +832,19 @@ def conv_wino24_pack_filter(w, want_dgrad=False):
     Cout, Cin, kh, kw = w.shape
     if (kh, kw) != (3, 3):
         raise KernelError("only 3x3 filters")
-    pf = torch.empty(L.ssad_conv_wino24_filter_floats(Cout, Cin), dtype=torch.float32, device="cuda")
-    pd = torch.empty(L.ssad_conv_wino24_filter_floats(Cin, Cout), dtype=torch.float32,
-                     device="cuda") if want_dgrad else None
+    if out is not None:         # (forward, data-gradient or None) to fill; decides instead of want_dgrad
+        pf, pd = out
+        want_dgrad = pd is not None
+    else:
+        pf = torch.empty(L.ssad_conv_wino24_filter_floats(Cout, Cin), dtype=torch.float32, device="cuda")
+        pd = torch.empty(L.ssad_conv_wino24_filter_floats(Cin, Cout), dtype=torch.float32,
+                         device="cuda") if want_dgrad else None
     tab = (PackEntry * 1)(PackEntry(w.data_ptr(), Cout, Cin, pf.data_ptr(), pd.data_ptr() if want_dgrad else 0))
     _check(L.ssad_conv_wino24_pack_filters(tab, 1, _stream()), "conv_wino24_pack_filters")
     return (pf, pd) if want_dgrad else pf
 
 
-def conv_split_pack_filter(w, want_dgrad=False):
+def conv_split_pack_filter(w, want_dgrad=False, out=None):
     """Split-operand (3 x fp16 MFMA) filter pack: header with the filter's |max| + hi / lo fp16 planes; want_dgrad:
     -> (forward, data-gradient) packs (conv3x3_split.hip)."""
     L = lib()
@@ -821,9 +852,13 @@ def conv_split_pack_filter(w, want_dgrad=False):
     Cout, Cin, kh, kw = w.shape
     if (kh, kw) != (3, 3):
         raise KernelError("only 3x3 filters")
-    pf = torch.empty(L.ssad_conv_split_filter_floats(Cout, Cin), dtype=torch.float32, device="cuda")
-    pd = torch.empty(L.ssad_conv_split_filter_floats(Cin, Cout), dtype=torch.float32,
-                     device="cuda") if want_dgrad else None
+    if out is not None:         # (forward, data-gradient or None) to fill; decides instead of want_dgrad
+        pf, pd = out
+        want_dgrad = pd is not None
+    else:
+        pf = torch.empty(L.ssad_conv_split_filter_floats(Cout, Cin), dtype=torch.float32, device="cuda")
+        pd = torch.empty(L.ssad_conv_split_filter_floats(Cin, Cout), dtype=torch.float32,
+                         device="cuda") if want_dgrad else None
     tab = (PackEntry * 1)(PackEntry(w.data_ptr(), Cout, Cin, pf.data_ptr(), pd.data_ptr() if want_dgrad else 0))
     _check(L.ssad_conv_split_pack_filters(tab, 1, _stream()), "conv_split_pack_filters")
     return (pf, pd) if want_dgrad else pf
@@ -842,8 +877,7 @@ def conv3x3_forward_split(xs, packed, bias, Cout, *, relu=False, sigmoid=False, 
     flags = (CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0) | (CONV_MASK_AUX if mask_by is not None else 0)
     arr = _conv_levels(xs, ys, mask_by)
     need = L.ssad_conv3x3_split_workspace_bytes(arr, len(xs), Cin)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device="cuda")
+    workspace = _own_workspace(workspace, need)
     _check(L.ssad_conv3x3_forward_split(arr, len(xs), _ptr(packed), _ptr(bias), Cout, Cin, flags, _ptr(workspace),
                                         workspace.numel(), _ptr(amax_in), _ptr(amax_out), _stream()),
            "conv3x3_forward_split")
@@ -1126,14 +1160,14 @@ def gemm_conv_desc(a, lda, x, y, K, M, bias=None, residual=None, mask=None, relu
                     (GEMM_RELU if relu else 0) | (GEMM_ACCUMULATE if accumulate else 0))
 
 
-def _run_gemm(d, what, split):
+def _run_gemm(d, what, split, workspace=None):
     """ssad_conv1x1_gemm, or (split) the same descriptor on the split-operand engine of gemm_split.hip"""
     L = lib()
     if not split:
         _check(L.ssad_conv1x1_gemm(C.byref(d), _stream()), what)
         return
     need = L.ssad_conv1x1_gemm_split_workspace_bytes(C.byref(d))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device="cuda")
+    ws = _own_workspace(workspace, need)
     _check(L.ssad_conv1x1_gemm_split(C.byref(d), _ptr(ws), ws.numel(), _stream()), what + " (split)")
 
 
@@ -1155,50 +1189,52 @@ def split_absmax_levels(xs, words=None):
     return words
 
 
-def gemm_split_pack_filter(a, lda, Kc, M):
+def gemm_split_pack_filter(a, lda, Kc, M, out=None):
     """The split copy of a pointwise filter operand a[Kc][lda] (ssad_gemm_split_pack_filters, one entry)."""
-    dst = torch.empty(lib().ssad_gemm_split_filter_floats(Kc, M), dtype=torch.float32, device="cuda")
+    dst = out if out is not None else torch.empty(lib().ssad_gemm_split_filter_floats(Kc, M), dtype=torch.float32,
+                                                  device="cuda")
     tab = (GemmPackEntry * 1)(GemmPackEntry(a.data_ptr(), dst.data_ptr(), lda, Kc, M))
     _check(lib().ssad_gemm_split_pack_filters(tab, 1, _stream()), "gemm_split_pack_filters")
     return dst
 
 
-def conv1x1_forward_split_amax(x, wt, M, bias=None, residual=None, relu=False, packed_a=None, x_amax=None, y_amax=None):
+def conv1x1_forward_split_amax(x, wt, M, bias=None, residual=None, relu=False, packed_a=None, x_amax=None, y_amax=None,
+                               out=None, workspace=None):
     """conv1x1_forward on the split-operand engine with the filter split / x's |max| word handed over and (y_amax: a
     zeroed int32[1]) the |max| of the result folded into a word (ssad_conv1x1_gemm_split_amax)."""
     _f32c(x, "x"); _f32c(wt, "wt")
     N, Kc, H, W = x.shape
-    y = torch.empty((N, M, H, W), dtype=torch.float32, device="cuda")
+    y = out if out is not None else torch.empty((N, M, H, W), dtype=torch.float32, device="cuda")
     d = gemm_conv_desc(wt, wt.shape[1], x, y, Kc, M, bias, residual, None, relu, False)
     L = lib()
     need = L.ssad_conv1x1_gemm_split_workspace_bytes(C.byref(d))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device="cuda")
+    ws = _own_workspace(workspace, need)
     _check(L.ssad_conv1x1_gemm_split_amax(C.byref(d), _ptr(packed_a), _ptr(x_amax), _ptr(y_amax), _ptr(ws), ws.numel(),
                                           _stream()), "conv1x1_gemm_split_amax")
     return y
 
 
-def conv1x1_forward(x, wt, M, bias=None, residual=None, relu=False, out=None, split=False):
+def conv1x1_forward(x, wt, M, bias=None, residual=None, relu=False, out=None, split=False, workspace=None):
     """act(conv1x1(x, W) + bias (+ residual)) with W^T from transpose_filter (x: N x K x H x W)."""
     _f32c(x, "x"); _f32c(wt, "wt")
     N, Kc, H, W = x.shape
     y = out if out is not None else torch.empty((N, M, H, W), dtype=torch.float32, device="cuda")
     d = gemm_conv_desc(wt, wt.shape[1], x, y, Kc, M, bias, residual, None, relu, False)
-    _run_gemm(d, "conv1x1_gemm", split)
+    _run_gemm(d, "conv1x1_gemm", split, workspace)
     return y
 
 
-def conv1x1_dgrad(dy, w, mask=None, accumulate_into=None, split=False):
+def conv1x1_dgrad(dy, w, mask=None, accumulate_into=None, split=False, out=None, workspace=None):
     """dX = W^T . dY (w: [M][C](x1x1) natural layout), optionally masked by mask > 0, optionally
-    added onto `accumulate_into`."""
+    added onto `accumulate_into` (else written to `out`)."""
     _f32c(dy, "dy")
     N, M, H, W = dy.shape
     Cc = w.shape[1]
     w2 = _f32c(w.reshape(M, Cc), "w")
-    dx = accumulate_into if accumulate_into is not None else torch.empty((N, Cc, H, W), dtype=torch.float32,
-                                                                     device="cuda")
+    dx = accumulate_into if accumulate_into is not None else out if out is not None else torch.empty(
+        (N, Cc, H, W), dtype=torch.float32, device="cuda")
     d = gemm_conv_desc(w2, Cc, dy, dx, M, Cc, None, None, mask, False, accumulate_into is not None)
-    _run_gemm(d, "conv1x1_gemm (dgrad)", split)
+    _run_gemm(d, "conv1x1_gemm (dgrad)", split, workspace)
     return dx
 
 
@@ -1224,32 +1260,34 @@ def conv1x1_wgrad(x, dy, out=None, accumulate=False, split=False, x_amax=None, d
     return dw
 
 
-def subsample(x, stride=2):
+def subsample(x, stride=2, out=None):
     _f32c(x, "x")
     N, Cc, H, W = x.shape
-    y = torch.empty((N, Cc, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.float32, device="cuda")
+    y = out if out is not None else torch.empty((N, Cc, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.float32,
+                                                device="cuda")
     _check(lib().ssad_subsample(_ptr(x), N, Cc, H, W, stride, _ptr(y), _stream()), "subsample")
     return y
 
 
-def subsample_grad(dy, H, W, stride=2, accumulate_into=None):
+def subsample_grad(dy, H, W, stride=2, accumulate_into=None, out=None):
     _f32c(dy, "dy")
     N, Cc = dy.shape[0], dy.shape[1]
-    dx = accumulate_into if accumulate_into is not None else torch.empty((N, Cc, H, W), dtype=torch.float32,
-                                                                     device="cuda")
+    dx = accumulate_into if accumulate_into is not None else out if out is not None else torch.empty(
+        (N, Cc, H, W), dtype=torch.float32, device="cuda")
     _check(lib().ssad_subsample_grad(_ptr(dy), N, Cc, H, W, stride, int(accumulate_into is not None), _ptr(dx),
                                      _stream()), "subsample_grad")
     return dx
 
 
-def grouped_conv3x3_pack_filter(w, group):
+def grouped_conv3x3_pack_filter(w, group, out=None):
     """[C][C/group][3][3] -> the grouped kernel's MFMA operand order."""
     _f32c(w, "w")
     Cc = w.shape[0]
     n = lib().ssad_grouped_conv3x3_filter_floats(Cc, group)
     if n < 0 or w.shape[1] * group != Cc:
         raise KernelError("grouped_conv3x3: %d channels in %d groups (4, 8, 16 or 32 per group)" % (Cc, group))
-    out = torch.empty(n, dtype=torch.float32, device="cuda")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
     _check(lib().ssad_grouped_conv3x3_pack_filter(_ptr(w), Cc, group, _ptr(out), _stream()), "grouped pack")
     return out
 
@@ -1269,13 +1307,14 @@ def grouped_conv3x3_forward(x, w, bias=None, group=64, stride=1, relu=False, out
     return y
 
 
-def conv_implicit_gemm(x, w, bias=None, stride=1, pad=0, relu=False, out=None, split_k=False):
-    """k x k convolution (group 1) as an implicit GEMM: x [N,C,H,W], w [M,C,k,k] -> [N,M,OH,OW]."""
+def conv_implicit_gemm(x, w, bias=None, stride=1, pad=0, relu=False, out=None, split_k=False, wt=None):
+    """k x k convolution (group 1) as an implicit GEMM: x [N,C,H,W], w [M,C,k,k] -> [N,M,OH,OW].  wt: where the
+    transposed filter [C*k*k][M rounded up to 4] goes."""
     _f32c(x, "x"); _f32c(w, "w")
     N, Cc, H, W = x.shape
     M, k = w.shape[0], w.shape[2]
     oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    wt = transpose_filter(w.reshape(M, Cc * k * k, 1, 1))
+    wt = transpose_filter(w.reshape(M, Cc * k * k, 1, 1), out=wt)
     y = out if out is not None else torch.empty((N, M, oh, ow), dtype=torch.float32, device="cuda")
     d = gemm_conv_desc(wt, wt.shape[1], x, y, Cc * k * k, M, bias, None, None, relu, False)
     d.P = oh * ow

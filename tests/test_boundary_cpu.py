@@ -372,6 +372,36 @@ def test_kernel_entry_points_refuse_bad_arguments_without_a_device(lib):
     assert raw.ssad_momentum_sgd_flat(p, p, p, p, 0.9, 1e-4, seg, 1, None, None) == -1      # row_scale without row_len
 
 
+def test_pointwise_geometry_rules_are_refusals_without_a_device(lib):
+    """The geometry rules the isolation suite (tests/test_gpu_isolation.py) leans on are checked before any launch:
+    ssad_conv1x1_gemm needs P % 4 == 0 and lda % 4 == 0 (a data gradient's lda is the layer's Cin), ssad_conv1x1_wgrad
+    P % 16 == 0, ssad_conv1x1_wgrad_split P % 8 == 0, ssad_conv_kxk_dgrad Cin * k * k % 4 == 0 -- odd channel counts and
+    the 7 x 9 map get SSAD_E_BADARG, not a kernel that reads past a row."""
+    from ssad_amd import kernels as K
+    raw = ctypes.CDLL(_capi.LIB_PATH)
+    vp, i32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    one = ctypes.create_string_buffer(4096)
+    p = ctypes.cast(one, vp).value // 16 * 16 + 16                    # the GEMM wants 16-byte aligned operands
+    raw.ssad_conv1x1_gemm.argtypes = [ctypes.POINTER(K.GemmConv), vp]
+
+    def gemm(lda, N, Kc, P, M):
+        return raw.ssad_conv1x1_gemm(ctypes.byref(K.GemmConv(p, p, p, 0, 0, 0, lda, N, Kc, P, M, 0)), None)
+
+    assert gemm(132, 2, 37, 63, 131) == -1          # forward 37 -> 131 on 7 x 9: P % 4
+    assert gemm(37, 2, 131, 48, 37) == -1           # its data gradient on 3 x 16: lda = Cin = 37
+    assert gemm(130, 2, 37, 48, 131) == -1          # lda % 4
+    raw.ssad_conv1x1_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]
+    assert raw.ssad_conv1x1_wgrad(p, p, 2, 24, 108, 40, p, 0, p, 1 << 20, None) == -1          # P % 16
+    raw.ssad_conv1x1_wgrad_split_workspace_bytes.restype = sz
+    raw.ssad_conv1x1_wgrad_split_workspace_bytes.argtypes = [i32] * 4
+    assert raw.ssad_conv1x1_wgrad_split_workspace_bytes(2, 37, 63, 131) == 0                   # P % 8: unsupported
+    assert raw.ssad_conv1x1_wgrad_split_workspace_bytes(2, 37, 48, 131) > 0
+    raw.ssad_conv1x1_wgrad_split.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]
+    assert raw.ssad_conv1x1_wgrad_split(p, p, 2, 37, 63, 131, p, 0, p, 1 << 20, None) == -1
+    raw.ssad_conv_kxk_dgrad.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, sz, vp]
+    assert raw.ssad_conv_kxk_dgrad(p, p, 2, 37, 7, 9, 131, 3, 2, 1, p, None, 0, p, 1 << 20, None) == -1   # 37 * 9 % 4
+
+
 def test_split_engine_entry_points_refuse_bad_arguments_without_a_device(lib):
     """Round 6: the split-operand engines validate before they launch -- the two |max| words of a filter gradient go
     together, workspaces are checked against the size queries, tensors of 2 GiB and more are sent back to the exact
