@@ -42,6 +42,7 @@ import torch
 from . import kernels as K
 from . import program as PR
 from .data_parallel import BucketedAllReduce
+from .engines import Engine, Switches, backbone_engine, conv_table, emit_packs, filter_floats, same_engine
 from .modeling.resnet_fpn import ChannelRatioError, channel_widths
 
 # pixels (all images) a pointwise launch needs before the split-operand GEMM pays (see NativeResNetFPN._gemm)
@@ -72,14 +73,14 @@ def student_widths(arch, channel_ratio, fpn_dim=256):
 
 class _Layer(object):
     __slots__ = ("name", "k", "cin", "cout", "stride", "train", "group", "affine", "w", "b", "gw", "gb", "wt",
-                 "pf", "pd", "s2", "f24")
+                 "pf", "pd", "s2", "engine")
 
     def __init__(self, name, k, cin, cout, stride, train, group=1, affine=False):
         self.name, self.k, self.cin, self.cout, self.stride, self.train = name, k, cin, cout, stride, train
         self.group = group
         self.affine = affine       # followed by a frozen AffineChannel (folded): the bias is not a parameter
         self.w = self.b = self.gw = self.gb = self.wt = self.pf = self.pd = self.s2 = None
-        self.f24 = False           # 3x3 forward on the F(2x4, 3x3) engine (frozen networks, >= 128 outputs)
+        self.engine = None         # engines.Engine of an ungrouped stride-1 3x3 layer (forward and data gradient)
 
     @property
     def wcin(self):
@@ -121,6 +122,7 @@ class NativeResNetFPN(object):
         # mixed-precision step whose gradients overflowed, head_pipeline.DistillHeadsF16)
         self.skip_flag = skip_flag
         self._overlap_wgrad = overlap_wgrad
+        self.switches = Switches.read()           # the one read of the engine switches
         self._build()
 
     @classmethod
@@ -364,9 +366,7 @@ class NativeResNetFPN(object):
             t = tensors[0]
             P.add(PR.SPLIT_ABSMAX, 73, p=(t, addr), l=(t.numel(),), work=4.0 * t.numel(), keep=[t])
         else:
-            arr = (K.ConvLevel * len(tensors))()
-            for i, t in enumerate(tensors):
-                arr[i] = K.ConvLevel(t.data_ptr(), 0, 0, t.shape[0], t.shape[2], t.shape[3], 0, 0)
+            arr = conv_table([(t, None, None, None, None) for t in tensors])
             P.add(PR.SPLIT_ABSMAX_LEVELS, 73, i=(len(tensors), channels, 0), p=(arr, addr),
                   work=4.0 * sum(t.numel() for t in tensors), keep=list(tensors))
         self._amax_groups[key] = base
@@ -413,7 +413,7 @@ class NativeResNetFPN(object):
         # same-box A/B pairs: K, M >= 128 costs the step +1.6 ms, >= 64 +3.2 ms (those layers are HBM-bound); at batch 2
         # (config 2: < 8192 pixels per launch from res4 up) the call's three extra small launches cost more than the
         # GEMM saves (+1.0 ms on a 12 ms step).
-        if self._gemm_split and Kc >= 256 and M >= 256 and px >= GEMM_SPLIT_MIN_PIXELS and klass == 50:
+        if self.switches.split_conv & 128 and Kc >= 256 and M >= 256 and px >= GEMM_SPLIT_MIN_PIXELS and klass == 50:
             nb = K.lib().ssad_conv1x1_gemm_split_workspace_bytes(C.byref(d))
             if nb:
                 self._split_need = max(self._split_need, nb)
@@ -437,47 +437,32 @@ class NativeResNetFPN(object):
             (self._gpack_train if train else self._gpack_frozen).append((a, lda, Kc, M, dst))
         return self._gemm_packs[key]
 
-    def _conv3(self, P, probs, Cout, Cin, flags, klass=48, f24=False, fold=False):
-        """probs: [(x, y, mask or None, packed, bias or None)]: independent 3x3 convolutions of one
-        (Cout, Cin) in one launch; f24: True = on the F(2x4, 3x3) engine (packs from ssad_conv_wino24_pack_filters),
-        "direct" = the direct kernel (packs from ssad_conv_pack_filter), False = F(2x2),
-        3 = on the split-operand engine (conv3x3_split.hip; its workspace is bound when the program is finished)."""
-        if f24 == 3:
-            arr = (K.ConvLevel * len(probs))()
-            for i, (x, y, mask, packed, bias) in enumerate(probs):
-                arr[i] = K.ConvLevel(x.data_ptr(), y.data_ptr(), mask.data_ptr() if mask is not None else 0,
-                                     x.shape[0], x.shape[2], x.shape[3], packed.data_ptr(),
-                                     bias.data_ptr() if bias is not None else 0)
+    # timing class of a 3x3 launch by (trained network?, engine)
+    KLASS3 = {(True, Engine.DIRECT): 18, (True, Engine.F22): 48, (True, Engine.F24): 46, (True, Engine.SPLIT): 66,
+              (False, Engine.DIRECT): 18, (False, Engine.F22): 48, (False, Engine.F24): 47, (False, Engine.SPLIT): 67}
+
+    def _conv3(self, P, probs, Cout, Cin, flags, engine, fold=False):
+        """probs: [(x, y, mask or None, packed, bias or None)]: independent 3x3 convolutions of one (Cout, Cin) in one
+        launch on one engine (the split-operand engine's workspace is bound when the program is finished)."""
+        arr = conv_table(probs)
+        px = sum(p[0].shape[0] * p[0].shape[2] * p[0].shape[3] for p in probs)
+        ptrs, sizes = (arr, None, None), ()
+        if engine == Engine.SPLIT:
             nb = K.lib().ssad_conv3x3_split_workspace_bytes(arr, len(probs), Cin)
-            self._split_need = max(getattr(self, "_split_need", 0), nb)
-            px = sum(p[0].shape[0] * p[0].shape[2] * p[0].shape[3] for p in probs)
+            self._split_need = max(self._split_need, nb)
             xa = self._amax_addr(self._measure(P, [p[0] for p in probs], Cin))
             ya = self._amax_addr(self._produces(*[p[1] for p in probs])) if (self._fwd or fold) else None
-            idx = P.add(PR.CONV3X3, 66 if self.train else 67, i=(len(probs), Cout, Cin, flags, 3), l=(nb,),
-                        p=(arr, None, None, None, xa, ya), work=2.0 * 9 * Cout * Cin * px,
-                        keep=[t for p in probs for t in p if t is not None])
+            ptrs, sizes = (arr, None, None, None, xa, ya), (nb,)
+        idx = P.add(PR.CONV3X3, self.KLASS3[self.train, engine], i=(len(probs), Cout, Cin, flags, engine), l=sizes,
+                    p=ptrs, work=2.0 * 9 * Cout * Cin * px, keep=[t for p in probs for t in p if t is not None])
+        if engine == Engine.SPLIT:
             self._split_ops.append(idx)
-            return
-        direct = f24 == "direct"
-        if direct:
-            klass, f24 = 18, False
-        if f24:
-            klass = 46 if self.train else 47
-        arr = (K.ConvLevel * len(probs))()
-        for i, (x, y, mask, packed, bias) in enumerate(probs):
-            arr[i] = K.ConvLevel(x.data_ptr(), y.data_ptr(), mask.data_ptr() if mask is not None else 0,
-                                 x.shape[0], x.shape[2], x.shape[3], packed.data_ptr(),
-                                 bias.data_ptr() if bias is not None else 0)
-        px = sum(p[0].shape[0] * p[0].shape[2] * p[0].shape[3] for p in probs)
-        P.add(PR.CONV3X3, klass, i=(len(probs), Cout, Cin, flags, 0 if direct else 2 if f24 else 1), p=(arr, None, None),
-              work=2.0 * 9 * Cout * Cin * px, keep=[t for p in probs for t in p if t is not None])
 
     def _wgrad3(self, P, x, dy, layer):
-        arr = (K.ConvLevel * 1)()
-        arr[0] = K.ConvLevel(x.data_ptr(), 0, dy.data_ptr(), x.shape[0], x.shape[2], x.shape[3], 0, 0)
+        arr = conv_table([(x, None, dy, None, None)])
         # SSAD_SPLIT_CONV bit 64 (default): the >= 256-wide 3x3 filter gradients on the split-operand engine (the
         # 128-wide res3 layers are level with the F(3x3, 2x2) engine there: 2 blocks of dW, 128 slabs to reduce)
-        split = (int(os.environ.get("SSAD_SPLIT_CONV", "511")) & 64) != 0 and layer.cout >= 256 and layer.cin >= 256
+        split = bool(self.switches.split_conv & 64) and layer.cout >= 256 and layer.cin >= 256
         if split and not K.lib().ssad_conv3x3_wgrad_split_workspace_bytes(arr, 1, layer.cout, layer.cin):
             split = False           # (a tensor of 2 GiB or more: the exact engine)
         size_fn = K.lib().ssad_conv3x3_wgrad_split_workspace_bytes if split else K.lib().ssad_conv3x3_wgrad_workspace_bytes
@@ -499,7 +484,7 @@ class NativeResNetFPN(object):
         pix = x.shape[2] * x.shape[3]
         # SSAD_SPLIT_CONV bit 256: the compute-bound pointwise filter gradients (C, M >= 256, the launch's pixels as for
         # the forward GEMM) on the split-operand engine (gemm_split.hip, wpoint_split_kernel)
-        split = ((int(os.environ.get("SSAD_SPLIT_CONV", "511")) & 256) != 0 and Cc >= 256 and layer.cout >= 256
+        split = (bool(self.switches.split_conv & 256) and Cc >= 256 and layer.cout >= 256
                  and N * pix >= GEMM_SPLIT_MIN_PIXELS and pix % 8 == 0)
         if split and not K.lib().ssad_conv1x1_wgrad_split_workspace_bytes(N, Cc, pix, layer.cout):
             split = False           # (a tensor of 2 GiB or more: the exact engine)
@@ -584,7 +569,6 @@ class NativeResNetFPN(object):
     # -- program construction ----------------------------------------------------------------------
     def _build(self):
         self._ws_need, self._ws_ops = 0, []
-        import os
         ov = self._overlap_wgrad
         on = os.environ.get("SSAD_OVERLAP_WGRAD", "1") == "1" if ov is None else ov
         # filter / bias gradients go round-robin over this many auxiliary streams (each with its own
@@ -604,28 +588,9 @@ class NativeResNetFPN(object):
         # packed filters: frozen layers once (prepare program), trainable layers every step (pack segment)
         prep, P = PR.Program(), PR.Program()
         self.prep, self.prog = prep, P
-        wino_frozen, wino_train, wino24_frozen, wino24_train = [], [], [], []
-        # A network that is only evaluated (the distillation step's frozen teacher) runs its 3x3 layers of >= 128
-        # outputs on the F(2x4, 3x3) engine: 3 multiplies per output instead of 4, fp32 error ~2e-6 of the output
-        # scale (conv3x3_winograd24.hip; SSAD_TEACHER_F24=0: the F(2x2) engine as in rounds 1-4)
-        use_f24 = (not self.train) and int(os.environ.get("SSAD_TEACHER_F24", "1")) >= 1
-        # SSAD_STUDENT_F24 bit 8 (default on): the TRAINED network's 3x3 layers of >= 128 channels too, forward and data
-        # gradient (the filter gradient keeps its F(3x3, 2x2) engine); DESIGN 3.10e has the error and step-time A/B
-        use_f24_train = self.train and (int(os.environ.get("SSAD_STUDENT_F24", "15")) & 8) != 0
-        # SSAD_SPLIT_CONV bit 16: the >= 256-wide stride-1 3x3 layers (res4, res5, FPN outputs) on the split-operand engine
-        # (default on: step -0.1 ... -1.3 ms in four same-box A/B pairs, profiles/r06_experiments.md)
-        use_split = (int(os.environ.get("SSAD_SPLIT_CONV", "511")) & 16) != 0 and (use_f24 or use_f24_train)
-        split_frozen, split_train = [], []
-        direct_frozen, direct_train = [], []
-
-        def accepts(floats, l):
-            """Does the engine whose pack-size function is `floats` take this layer's widths (forward, and the
-            data gradient's transposed widths when it is trained)?  A refusal (size 0) sends the layer to the next
-            engine of the chain below, the rule of the split filter gradient (_wgrad3)."""
-            return floats(l.cout, l.cin) > 0 and (not l.train or floats(l.cin, l.cout) > 0)
+        packs = {True: {}, False: {}}          # {trained?: {Engine: pack entries}}: P packs every step, prep once
         self._split_ops, self._split_need = [], 0
         self._gemm_split_ops = []
-        self._gemm_split = (int(os.environ.get("SSAD_SPLIT_CONV", "511")) & 128) != 0
         self.amax = torch.zeros(self.AMAX_WORDS, dtype=torch.int32, device=self.device)
         self._amax_groups, self._amax_next = {}, 0
         self._gemm_packs, self._gpack_train, self._gpack_frozen, self._a_train = {}, [], [], {}
@@ -647,34 +612,12 @@ class NativeResNetFPN(object):
                 # gradients read the filter in its natural layout)
                 l.wt = self._t(l.cin * 9, l.cout)
                 trs.append((l.w, l.wt, l.cout, l.cin * 9, l.cout))
-            elif (l.k == 3 and use_split and l.cout >= 256 and l.cin >= 256
-                  and accepts(lib.ssad_conv_split_filter_floats, l)):
-                l.pf = self._t(lib.ssad_conv_split_filter_floats(l.cout, l.cin))
-                l.pd = self._t(lib.ssad_conv_split_filter_floats(l.cin, l.cout)) if l.train else None
-                l.f24 = 3
-                (split_train if l.train else split_frozen).append(l)
-            elif l.k == 3 and use_f24 and not l.train and l.cout >= 128 and accepts(lib.ssad_conv_wino24_filter_floats, l):
-                l.pf = self._t(lib.ssad_conv_wino24_filter_floats(l.cout, l.cin))
-                l.f24 = True
-                wino24_frozen.append(l)
-            elif (l.k == 3 and use_f24_train and l.train and l.cout >= 128 and l.cin >= 128
-                  and accepts(lib.ssad_conv_wino24_filter_floats, l)):
-                l.pf = self._t(lib.ssad_conv_wino24_filter_floats(l.cout, l.cin))
-                l.pd = self._t(lib.ssad_conv_wino24_filter_floats(l.cin, l.cout))
-                l.f24 = True
-                wino24_train.append(l)
-            elif l.k == 3 and (l.cout < 32 or l.cin < 32 or not accepts(lib.ssad_conv_wino_filter_floats, l)):
-                # narrower than one 32-row tile of the F(2x2) engine (res2 of a quarter-width student, 16 -> 16): the
-                # direct kernel, the subnets' rule for outputs below 32 channels (head_pipeline._use_wino)
-                l.pf = self._t(lib.ssad_conv_packed_filter_floats(l.cout, l.cin))
-                l.pd = self._t(lib.ssad_conv_packed_filter_floats(l.cin, l.cout)) if l.train else None
-                l.f24 = "direct"
-                (direct_train if l.train else direct_frozen).append(l)
             elif l.k == 3:
-                l.pf = self._t(lib.ssad_conv_wino_filter_floats(l.cout, l.cin))
-                need_pd = l.train                  # every trainable 3x3 sends a gradient further down
-                l.pd = self._t(lib.ssad_conv_wino_filter_floats(l.cin, l.cout)) if need_pd else None
-                (wino_train if l.train else wino_frozen).append(l)
+                l.engine = backbone_engine(self.switches, l.train, l.cout, l.cin)
+                l.pf = self._t(filter_floats(l.engine)(l.cout, l.cin))
+                # (every trainable 3x3 sends a gradient further down)
+                l.pd = self._t(filter_floats(l.engine)(l.cin, l.cout)) if l.train else None
+                packs[l.train].setdefault(l.engine, []).append((l.w, l.cout, l.cin, l.pf, l.pd))
             else:                                                    # stem: [147][64]
                 l.wt = self._t(l.cin * l.k * l.k, l.cout)
                 trs.append((l.w, l.wt, l.cout, l.cin * l.k * l.k, l.cout))
@@ -688,37 +631,8 @@ class NativeResNetFPN(object):
                     tab[i] = K.TransposeEntry(w.data_ptr(), wt.data_ptr(), M, Kc, ldm, 0)
                 tgt.add(PR.TRANSPOSE_FILTERS, 54, i=(len(trs),), p=(tab,),
                         work=8.0 * sum(M * Kc for (_, _, M, Kc, _) in trs), keep=[t for e in trs for t in e[:2]])
-        for tgt, ls in ((prep, wino_frozen), (P, wino_train)):
-            if ls:
-                tab = (K.PackEntry * len(ls))()
-                for i, l in enumerate(ls):
-                    tab[i] = K.PackEntry(l.w.data_ptr(), l.cout, l.cin, l.pf.data_ptr(),
-                                         l.pd.data_ptr() if l.pd is not None else 0)
-                tgt.add(PR.WINO_PACK_FILTERS, 54, i=(len(ls),), p=(tab,),
-                        work=4.0 * sum(l.w.numel() + l.pf.numel() + (l.pd.numel() if l.pd is not None else 0)
-                                       for l in ls))
-        for tgt, ls in ((prep, wino24_frozen), (P, wino24_train)):
-            if ls:
-                tab = (K.PackEntry * len(ls))()
-                for i, l in enumerate(ls):
-                    tab[i] = K.PackEntry(l.w.data_ptr(), l.cout, l.cin, l.pf.data_ptr(),
-                                         l.pd.data_ptr() if l.pd is not None else 0)
-                tgt.add(PR.WINO_PACK_FILTERS, 54, i=(len(ls), 2), p=(tab,),
-                        work=4.0 * sum(l.w.numel() + l.pf.numel() + (l.pd.numel() if l.pd is not None else 0)
-                                       for l in ls))
-        for tgt, ls in ((prep, split_frozen), (P, split_train)):
-            if ls:
-                tab = (K.PackEntry * len(ls))()
-                for i, l in enumerate(ls):
-                    tab[i] = K.PackEntry(l.w.data_ptr(), l.cout, l.cin, l.pf.data_ptr(),
-                                         l.pd.data_ptr() if l.pd is not None else 0)
-                tgt.add(PR.WINO_PACK_FILTERS, 54, i=(len(ls), 3), p=(tab,),
-                        work=4.0 * sum(l.w.numel() + l.pf.numel() + (l.pd.numel() if l.pd is not None else 0)
-                                       for l in ls))
-        for tgt, ls in ((prep, direct_frozen), (P, direct_train)):
-            for l in ls:
-                tgt.add(PR.PACK_FILTER, 54, i=(l.cout, l.cin), p=(l.w, l.pf, l.pd),
-                        work=4.0 * (l.w.numel() + l.pf.numel() + (l.pd.numel() if l.pd is not None else 0)))
+        for tgt, train in ((prep, False), (P, True)):
+            emit_packs(tgt, 54, packs[train], (Engine.F22, Engine.F24, Engine.SPLIT, Engine.DIRECT))
         # the pointwise filters' split copies (which layers need one is known once the passes are emitted: the table is
         # filled in below)
         gp_max = 2 * sum(1 for l in L.values() if l.k == 1)
@@ -805,7 +719,7 @@ class NativeResNetFPN(object):
                 P.add(PR.GROUPED_CONV3X3, 56, i=(N, cmid, y1.shape[2], y1.shape[3], l2.group, l2.stride, 1),
                       p=(y1, l2.pf, l2.b, y2), work=2.0 * 9 * cmid * l2.wcin * y2.shape[0] * h * w)
             else:
-                self._conv3(P, [(y1, y2, None, l2.pf, l2.b)], cmid, cmid, K.CONV_RELU, f24=l2.f24)
+                self._conv3(P, [(y1, y2, None, l2.pf, l2.b)], cmid, cmid, K.CONV_RELU, l2.engine)
             sc = xs
             if proj:
                 lp = L[pre + ".proj"]
@@ -831,7 +745,7 @@ class NativeResNetFPN(object):
         p5, p4, p3 = (self._like(t) for t in (t5, t4, t3))
         self._conv3(P, [(t, p, None, L[name].pf, L[name].b)                # three filters, one launch
                         for t, p, name in ((t5, p5, "out.0"), (t4, p4, "out.1"), (t3, p3, "out.2"))], D, D, 0,
-                   f24=L["out.0"].f24)
+                   same_engine(L[name].engine for name in ("out.0", "out.1", "out.2")))
         l6, l7 = L["p6"], L["p7"]
         if self._strided_own:
             # P6 / P7 (3x3, stride 2) at their own size
@@ -845,13 +759,13 @@ class NativeResNetFPN(object):
         else:
             # SSAD_STRIDED_3X3=winograd: stride-1 convolution, then the even positions
             p6f = self._t(N, D, c5.shape[2], c5.shape[3])
-            self._conv3(P, [(c5, p6f, None, l6.pf, l6.b)], D, l6.cin, 0, f24=l6.f24)
+            self._conv3(P, [(c5, p6f, None, l6.pf, l6.b)], D, l6.cin, 0, l6.engine)
             p6 = self._t(N, D, c5.shape[2] // 2, c5.shape[3] // 2)
             self._ew(P, PR.SUBSAMPLE, i=(N, D, c5.shape[2], c5.shape[3], 2), p=(p6f, p6), nbytes=8.0 * p6.numel())
             r6 = self._like(p6)
             self._ew(P, PR.RELU, p=(p6, r6), l=(p6.numel(),), nbytes=8.0 * p6.numel())
             p7f = self._like(p6)
-            self._conv3(P, [(r6, p7f, None, l7.pf, l7.b)], D, D, 0, f24=l7.f24)
+            self._conv3(P, [(r6, p7f, None, l7.pf, l7.b)], D, D, 0, l7.engine)
             p7 = self._t(N, D, (p6.shape[2] + 1) // 2, (p6.shape[3] + 1) // 2)
             self._ew(P, PR.SUBSAMPLE, i=(N, D, p6.shape[2], p6.shape[3], 2), p=(p7f, p7), nbytes=8.0 * p7.numel())
         self.fpn = [p3, p4, p5, p6, p7]                   # finest first (synth.LEVEL_SHAPES_*)
@@ -884,23 +798,23 @@ class NativeResNetFPN(object):
             self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, D, d7f.shape[2], d7f.shape[3], 2, 0), p=(d7, d7f), nbytes=4.0 * d7f.numel())
             self._wgrad3(P, r6, d7f, l7)
             dr6 = self._like(r6)
-            self._conv3(P, [(d7f, dr6, r6, l7.pd, None)], D, D, K.CONV_MASK_AUX, f24=l7.f24)   # masked by p6 > 0
+            self._conv3(P, [(d7f, dr6, r6, l7.pd, None)], D, D, K.CONV_MASK_AUX, l7.engine)   # masked by p6 > 0
             ptrs = (C.c_void_p * 2)(d6.data_ptr(), dr6.data_ptr())
             P.add(PR.SUM_N, 51, i=(2,), l=(d6.numel(),), p=(ptrs, d6), work=12.0 * d6.numel(), keep=[d6, dr6])
             # P6 = sub(conv(c5))
             d6f = self._like(S["p6f"])
             self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, D, d6f.shape[2], d6f.shape[3], 2, 0), p=(d6, d6f), nbytes=4.0 * d6f.numel())
             self._wgrad3(P, c5, d6f, l6)
-            self._conv3(P, [(d6f, dc5, None, l6.pd, None)], l6.cin, D, 0, f24=l6.f24)
+            self._conv3(P, [(d6f, dc5, None, l6.pd, None)], l6.cin, D, 0, l6.engine)
         # output convs: filter gradients and the three data gradients in one launch
         dt5, dt4, dt3 = self._like(t5), self._like(t4), self._like(t3)
-        if L["out.0"].f24 == 3:
+        if L["out.0"].engine == Engine.SPLIT:
             self._measure(P, [d5, d4, d3], D)          # one pass for the three filter gradients and the data gradient
         for t, d, name in ((t5, d5, "out.0"), (t4, d4, "out.1"), (t3, d3, "out.2")):
             self._wgrad3(P, t, d, L[name])
         self._conv3(P, [(d, dt, None, L[name].pd, None)
                         for d, dt, name in ((d5, dt5, "out.0"), (d4, dt4, "out.1"), (d3, dt3, "out.2"))], D, D, 0,
-                   f24=L["out.0"].f24)
+                   same_engine(L[name].engine for name in ("out.0", "out.1", "out.2")))
         # top-down path: t3 = lat2(c3) + up(t4), t4 = lat1(c4) + up(t5)
         up4, up5 = self._like(t4), self._like(t5)
         self._ew(P, PR.UPSAMPLE_GRAD, i=(N, D, t4.shape[2], t4.shape[3], 2), p=(dt3, up4), nbytes=5.0 * dt3.numel())
@@ -949,7 +863,7 @@ class NativeResNetFPN(object):
             self._gemm(P, l3.w.view(cout, cmid), cmid, dz, dz2, cout, cmid, mask=y2, fold=True)
             self._wgrad3(P, y1, dz2, l2)                                   # + bias gradient of c2
             dz1 = self._like(y1)
-            self._conv3(P, [(dz2, dz1, y1, l2.pd, None)], cmid, cmid, K.CONV_MASK_AUX, f24=l2.f24, fold=True)
+            self._conv3(P, [(dz2, dz1, y1, l2.pd, None)], cmid, cmid, K.CONV_MASK_AUX, l2.engine, fold=True)
             self._wgrad1(P, xs, dz1, l1)
             first_trainable = (stage == 3 and j == 0)
             if proj:

@@ -1,0 +1,152 @@
+"""Which engine runs a 3x3 convolution of the native fp32 pipelines (head_pipeline.DistillHeads,
+backbone_pipeline.NativeResNetFPN): the engine type, the one read of the environment switches, the rule of each
+pipeline, and the two tables (ssad_pack_entry[], ssad_conv_level[]) both pipelines hand to the kernels.
+
+A pipeline reads the switches once, at construction, asks the rule for every convolution before it allocates
+anything, packs each filter in the layout of the planned engine and launches the planned engine on it.  DESIGN.md
+section 3.7a has the rules as tables.
+"""
+import collections
+import enum
+import os
+
+from . import kernels as K
+from . import program as PR
+
+
+class Engine(enum.IntEnum):
+    """i[4] of a CONV3X3 record (csrc/pipeline/program.cc)."""
+    DIRECT = 0      # conv3x3.hip: any width, the parity floor
+    F22 = 1         # conv3x3_winograd.hip, F(2x2, 3x3): 4 multiplies per output, from 32 outputs
+    F24 = 2         # conv3x3_winograd24.hip, F(2x4, 3x3): 3 multiplies per output, fp32 error ~2e-6 of the output scale
+    SPLIT = 3       # conv3x3_split.hip: fp32 operands as hi + lo fp16, three fp16 MFMAs per pair; meets the direct
+    #                 kernel's parity floor where F(2x4) needs 2e-5
+
+
+# WINO_PACK_FILTERS numbers its layouts in i[1] (absent = 0 = F(2x2)); the direct engine's packs are PACK_FILTER records
+_PACK_LAYOUT = {Engine.F22: 0, Engine.F24: 2, Engine.SPLIT: 3}
+
+
+def filter_floats(engine):
+    """The library function (cout, cin) -> floats of a filter packed for this engine (0: the engine refuses the widths)."""
+    L = K.lib()
+    return {Engine.DIRECT: L.ssad_conv_packed_filter_floats, Engine.F22: L.ssad_conv_wino_filter_floats,
+            Engine.F24: L.ssad_conv_wino24_filter_floats, Engine.SPLIT: L.ssad_conv_split_filter_floats}[engine]
+
+
+class Switches(collections.namedtuple("Switches", "wino teacher_f24 student_f24 split_conv")):
+    """The four engine switches as the environment gives them.
+
+    SSAD_CONV_ENGINE=direct (wino False): the subnets on the direct kernel everywhere.
+
+    SSAD_TEACHER_F24: the frozen teacher on the F(2x4) engine (admissible where nothing back-propagates): 1 (default)
+    its cls_pred layer and its backbone's 3x3 layers of >= 128 outputs; 2: also its tower layers, which then leave
+    the launch they shared with the student's; 0 = everything on F(2x2) as in rounds 1-4.
+
+    SSAD_STUDENT_F24, a bit mask (default 15; DESIGN 3.10e has the error and step-time A/B): the TRAINED networks on
+    F(2x4): 1 = the subnets' data gradients, 2 = cls_pred forward, 4 = tower forward (with the teacher's towers, one
+    launch), 8 = the backbone's 3x3 layers of >= 128 channels, forward and data gradient (the filter gradient keeps
+    its F(3x3, 2x2) engine).
+
+    SSAD_SPLIT_CONV, a bit mask: the split-operand engines where they measured faster than F(2x4) at config 3's size:
+    1 = cls_pred forward (student and teacher), 2 = its data gradient, 4 = tower forward (both networks, one launch per
+    depth), 8 = tower data gradients, 16 = the backbones' >= 256-wide 3x3 layers, 32 = the subnets' >= 128-wide filter
+    gradients (conv3x3_wgrad_split.hip), 64 = the backbones' >= 256-wide ones, 128 = the backbones' pointwise layers
+    with K, M >= 256 on the split-operand GEMM, 256 = their filter gradients (gemm_split.hip); 0 = off.  Default 511:
+    same-box A/B of the step 86.0 -> 83.9 ms for bits 1-16 (every bit pays in the step although the isolated launches
+    are level with F(2x4): the step is power-bound, and the engine spends less of it; bit 16 alone -0.1 ... -1.3 ms in
+    four pairs), 82.6 -> 78.3 ms for bits 32 + 64, 78.9 -> 73.5 ms for bit 128, 72.6 -> 70.4 ms for bit 256
+    (profiles/r06_experiments.md)."""
+    __slots__ = ()
+
+    @classmethod
+    def read(cls, env=None):
+        env = os.environ if env is None else env
+        return cls(env.get("SSAD_CONV_ENGINE", "winograd").lower() != "direct", int(env.get("SSAD_TEACHER_F24", "1")),
+                   int(env.get("SSAD_STUDENT_F24", "15")), int(env.get("SSAD_SPLIT_CONV", "511")))
+
+    def for_subnets(self, distill, f16=False):
+        """What the subnets make of the switches.  The fp16-storage subnets have kernels of their own, and the direct
+        engine has no variants: all masks 0.  The towers of one depth (teacher + student) are ONE launch on ONE
+        engine when their widths agree: bit 4 of SSAD_STUDENT_F24 takes the teacher's towers along; with the teacher
+        pinned to F(2x2) (SSAD_TEACHER_F24=0) a distillation step keeps the shared launch there and bit 4 is void."""
+        if f16 or not self.wino:
+            return self._replace(teacher_f24=0, student_f24=0, split_conv=0)
+        teacher, student = self.teacher_f24, self.student_f24 & 7
+        if student & 4:
+            if teacher:
+                teacher = 2
+            elif distill:
+                student &= ~4
+        return self._replace(teacher_f24=teacher, student_f24=student)
+
+
+def subnet_engine(sw, who, name, cout, cin, which):
+    """Engine of one subnet convolution.  sw: Switches.for_subnets(); who = "teacher" | "student"; name: the layer's
+    (retnet_{cls,bbox}_{conv_n<i>,pred}_fpn<k>); which = "fwd" (a launch cin -> cout) | "dgrad" (cout -> cin)."""
+    fwd = which == "fwd"
+    if not sw.wino or (cout if fwd else cin) < 32:
+        return Engine.DIRECT           # narrower than one 32-row tile of the Winograd engines
+    pred = "_pred_" in name
+    if "bbox_pred" not in name and sw.split_conv & ((1 if fwd else 2) if pred else (4 if fwd else 8)):
+        return Engine.SPLIT
+    if who == "teacher":
+        f24 = fwd and cout >= 128 and sw.teacher_f24 >= (1 if pred else 2)
+    elif fwd:
+        f24 = cout >= 128 and sw.student_f24 & (2 if pred else 4)
+    else:
+        f24 = cin >= 128 and sw.student_f24 & 1
+    return Engine.F24 if f24 else Engine.F22
+
+
+def backbone_engine(sw, train, cout, cin):
+    """Engine of a backbone's ungrouped stride-1 3x3 layer, forward and (trained) data gradient alike.  sw: the
+    switches as read.  An engine whose pack-size function refuses the layer's widths (forward, and the data
+    gradient's transposed widths when it is trained) sends the layer to the next engine of the chain, the rule of the
+    split filter gradient."""
+    def accepts(engine):
+        return filter_floats(engine)(cout, cin) > 0 and (not train or filter_floats(engine)(cin, cout) > 0)
+    f24_on = bool(sw.student_f24 & 8) if train else sw.teacher_f24 >= 1
+    if sw.split_conv & 16 and f24_on and cout >= 256 and cin >= 256 and accepts(Engine.SPLIT):
+        return Engine.SPLIT
+    if f24_on and cout >= 128 and (cin >= 128 or not train) and accepts(Engine.F24):
+        return Engine.F24
+    if cout < 32 or cin < 32 or not accepts(Engine.F22):
+        # narrower than one 32-row tile of the F(2x2) engine (res2 of a quarter-width student, 16 -> 16)
+        return Engine.DIRECT
+    return Engine.F22
+
+
+def same_engine(engines):
+    """The one engine of a launch; problems planned on different engines cannot share one."""
+    engines = set(engines)
+    if len(engines) != 1:
+        raise K.KernelError("one launch, several engines: %s" % sorted(e.name for e in engines))
+    return engines.pop()
+
+
+def conv_table(rows):
+    """rows: [(x, y, aux, packed, bias)], tensors or None -> ssad_conv_level[]"""
+    arr = (K.ConvLevel * len(rows))()
+    for k, (x, y, aux, packed, bias) in enumerate(rows):
+        arr[k] = K.ConvLevel(x.data_ptr(), *[t.data_ptr() if t is not None else 0 for t in (y, aux)],
+                             x.shape[0], x.shape[2], x.shape[3],
+                             *[t.data_ptr() if t is not None else 0 for t in (packed, bias)])
+    return arr
+
+
+def emit_packs(P, klass, packs, order):
+    """packs: {Engine: [(w, cout, cin, packed_fwd or None, packed_dgrad or None)]}: one WINO_PACK_FILTERS launch per
+    layout, one PACK_FILTER record per filter of the direct engine, in this order of engines."""
+    for engine in order:
+        entries = packs.get(engine, ())
+        moved = [4 * (w.numel() + sum(t.numel() for t in (pf, pd) if t is not None)) for w, _, _, pf, pd in entries]
+        if engine == Engine.DIRECT:
+            for (w, cout, cin, pf, pd), nbytes in zip(entries, moved):
+                P.add(PR.PACK_FILTER, klass, i=(cout, cin), p=(w, pf, pd), work=nbytes)
+        elif entries:
+            tab = (K.PackEntry * len(entries))()
+            for k, (w, cout, cin, pf, pd) in enumerate(entries):
+                tab[k] = K.PackEntry(w.data_ptr(), cout, cin, *[t.data_ptr() if t is not None else 0 for t in (pf, pd)])
+            P.add(PR.WINO_PACK_FILTERS, klass, i=(len(entries), _PACK_LAYOUT[engine]), p=(tab,), work=sum(moved),
+                  keep=[t for w, _, _, pf, pd in entries for t in (w, pf, pd) if t is not None])

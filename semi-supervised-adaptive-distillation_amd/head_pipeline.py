@@ -22,6 +22,7 @@ through the workspace (tests check that), but scheduled MI355X-first:
 torch provides device memory, streams and torch.distributed only.
 """
 import dataclasses
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -33,6 +34,7 @@ from . import kernels as K
 from . import program as PR
 from . import synth
 from .data_parallel import BucketedAllReduce
+from .engines import Engine, Switches, conv_table, emit_packs, filter_floats, same_engine, subnet_engine
 from .modeling.retinanet_heads import HeadConfig
 
 
@@ -105,35 +107,8 @@ class DistillHeads(object):
         self.N, self.shapes, self.device = N, list(shapes), device
         self.distill = bool(distill)
         self.teacher_bbox_tower = teacher_bbox_tower and self.distill
-        import os
-        self.wino = os.environ.get("SSAD_CONV_ENGINE", "winograd").lower() != "direct"
-        # The frozen teacher on the F(2x4, 3x3) engine (conv3x3_winograd24.hip: 3 multiplies per output instead of
-        # F(2x2)'s 4, fp32 error ~2e-6 of the output scale -- admissible where nothing back-propagates):
-        #   1 (default) its cls_pred layer;  2: also its tower layers, which then leave the launch they shared with the
-        #   student's (SSAD_TEACHER_F24; 0 = everything on the F(2x2) engine as in rounds 1-4)
-        self.teacher_f24 = int(os.environ.get("SSAD_TEACHER_F24", "1")) if (self.wino and not self.F16) else 0
-        # the TRAINED subnets on the F(2x4) engine, a bit mask: 1 = data gradients, 2 = cls_pred forward,
-        # 4 = tower forward (with the teacher's towers, one launch)
-        self.student_f24 = int(os.environ.get("SSAD_STUDENT_F24", "15")) & 7 if (self.wino and not self.F16) else 0
-        # The towers of one depth (teacher + student) are ONE launch on ONE engine, and a filter is packed in the
-        # layout of the engine that reads it: decide once.  Bit 4 takes the teacher's towers along; with the teacher
-        # pinned to F(2x2) (SSAD_TEACHER_F24=0) a distillation step keeps the shared launch there and bit 4 is void.
-        if self.student_f24 & 4:
-            if self.teacher_f24:
-                self.teacher_f24 = 2
-            elif self.distill:
-                self.student_f24 &= ~4
-        # The split-operand engine (conv3x3_split.hip: fp32 operands as hi + lo fp16, three fp16 MFMAs per pair; meets the
-        # direct kernel's parity floor where F(2x4) needs 2e-5) where it measured faster than F(2x4) at config 3's size --
-        # bit mask SSAD_SPLIT_CONV: 1 = cls_pred forward (student and teacher), 2 = its data gradient, 4 = tower forward
-        # (both networks, one launch per depth), 8 = tower data gradients (16: the backbones' >= 256-wide 3x3 layers,
-        # backbone_pipeline.py), 32 = the subnets' >= 128-wide filter gradients (conv3x3_wgrad_split.hip; 64: the
-        # backbones' >= 256-wide ones; 128: the backbones' pointwise layers with K, M >= 256 on the split-operand GEMM,
-        # 256: their filter gradients, gemm_split.hip); 0 = off.  Default 511: same-box A/B of the step 86.0 -> 83.9 ms
-        # for bits 1-16 (every bit pays in the step although the isolated launches are level with F(2x4): the step is
-        # power-bound, and the engine spends less of it), 82.6 -> 78.3 ms for bits 32 + 64, 78.9 -> 73.5 ms for bit 128,
-        # 72.6 -> 70.4 ms for bit 256 (profiles/r06_experiments.md).
-        self.split_conv = int(os.environ.get("SSAD_SPLIT_CONV", "511")) if (self.wino and not self.F16) else 0
+        self.switches = Switches.read().for_subnets(self.distill, self.F16)     # the one read of the engine switches
+        self.split_conv = self.switches.split_conv
         self._split_ops, self._split_ws_need = [], 0
         self.momentum, self.weight_decay = momentum, weight_decay
         self.pg, self.world_size = process_group, world_size
@@ -144,8 +119,9 @@ class DistillHeads(object):
         if self.Dt != self.D and self.F16:
             raise K.KernelError("DistillHeadsF16: teacher_fpn_dim %d != fpn_dim %d is not supported (the fp16 subnets "
                                 "run teacher and student towers as one launch of one width)" % (self.Dt, self.D))
-        self.params = FlatParams(cfg, device, student_init)
         t_cfg = cfg if self.Dt == self.D else dataclasses.replace(cfg, fpn_dim=self.Dt)
+        self._plan_engines(cfg, t_cfg if self.distill else None)
+        self.params = FlatParams(cfg, device, student_init)
         self.teacher = FlatParams(t_cfg, device, teacher_init) if self.distill else None
         self.grads = FlatParams(cfg, device)
         self.moms = FlatParams(cfg, device)
@@ -206,30 +182,30 @@ class DistillHeads(object):
         names.append("retnet_%s_pred_fpn%d" % (tower, cfg.k_min))
         return names
 
-    # Engine choice per convolution: the Winograd F(2x2,3x3) kernel wherever the output is
-    # >= 32 channels wide (every layer of the reference configuration), the direct kernel
-    # below that.  SSAD_CONV_ENGINE=direct forces the direct kernel everywhere.
-    def _use_wino(self, cout):
-        return self.wino and cout >= 32
+    def _plan_engines(self, cfg, t_cfg):
+        """The engine of every convolution, before a buffer or a record exists: fwd_engine[who, layer] for the forward
+        launches of who = "student" | "teacher" (t_cfg None: no teacher), dgrad_engine[layer] for the student's data
+        gradients.  Filters are packed for these engines (_alloc_packed) and the launches read them on these
+        (_emit_forward, _emit_backward): nothing else decides."""
+        self.fwd_engine, self.dgrad_engine = {}, {}
+        for who, c in (("student", cfg), ("teacher", t_cfg)):
+            for name, shape, is_bias, _ in head_param_specs(c) if c is not None else ():
+                if not is_bias:
+                    layer, (cout, cin) = name[:-2], shape[:2]
+                    self.fwd_engine[who, layer] = subnet_engine(self.switches, who, layer, cout, cin, "fwd")
+                    if who == "student":
+                        self.dgrad_engine[layer] = subnet_engine(self.switches, who, layer, cout, cin, "dgrad")
 
     def _px(self):
         return self.N * sum(h * w for h, w in self.shapes)
 
     # -- program construction ---------------------------------------------------------
-    def _conv_table(self, problems):
-        """problems: [(xs, outs, masks or None, packed or None, bias or None)] -> ssad_conv_level[]"""
-        n = sum(len(p[0]) for p in problems)
-        arr = (K.ConvLevel * n)()
-        k = 0
-        for xs, outs, masks, packed, bias in problems:
-            for l, x in enumerate(xs):
-                arr[k] = K.ConvLevel(x.data_ptr(), outs[l].data_ptr() if outs is not None else 0,
-                                     masks[l].data_ptr() if masks is not None else 0,
-                                     x.shape[0], x.shape[2], x.shape[3],
-                                     packed.data_ptr() if packed is not None else 0,
-                                     bias.data_ptr() if bias is not None else 0)
-                k += 1
-        return arr
+    @staticmethod
+    def _conv_table(problems):
+        """problems: [(xs, outs or None, masks or None, packed or None, bias or None)], one tensor per level in xs / outs /
+        masks -> ssad_conv_level[], the problems' levels one after the other"""
+        return conv_table([(x, outs[l] if outs is not None else None, masks[l] if masks is not None else None, packed, bias)
+                           for xs, outs, masks, packed, bias in problems for l, x in enumerate(xs)])
 
     # -- |max| words of the split-operand engines (as backbone_pipeline._measure / _produces) ------------------------
     # One table per pipeline, zeroed by one fill at the start of the forward segment.  A launch's words are one
@@ -268,37 +244,60 @@ class DistillHeads(object):
                   work=4.0 * sum(t.numel() for l in lists for t in l), keep=[t for l in lists for t in l], stream=0)
         return base
 
-    def _emit_conv(self, P, problems, Cout, Cin, flags, klass, f24=False, split=False):
-        """One launch of independent convolutions of equal (Cout, Cin); f24: on the F(2x4, 3x3) engine; split: on the
-        split-operand engine (its workspace is bound by _finish_workspaces)."""
+    # timing class of a launch by (role, engine); "teacher_...": a launch of the teacher's problems alone.  The direct
+    # engine has one class for every role (18).
+    KLASS = {("tower", Engine.F22): 2, ("tower", Engine.F24): 23, ("tower", Engine.SPLIT): 28,
+             ("teacher_tower", Engine.F22): 2, ("teacher_tower", Engine.F24): 21, ("teacher_tower", Engine.SPLIT): 28,
+             ("cls_pred", Engine.F22): 3, ("cls_pred", Engine.F24): 22, ("cls_pred", Engine.SPLIT): 26,
+             ("teacher_cls_pred", Engine.F22): 3, ("teacher_cls_pred", Engine.F24): 20,
+             ("teacher_cls_pred", Engine.SPLIT): 25,
+             ("bbox_pred", Engine.F22): 4, ("teacher_bbox_pred", Engine.F22): 4,
+             ("pred_dgrad", Engine.F22): 16, ("pred_dgrad", Engine.F24): 24, ("pred_dgrad", Engine.SPLIT): 27,
+             ("tower_dgrad", Engine.F22): 16, ("tower_dgrad", Engine.F24): 24, ("tower_dgrad", Engine.SPLIT): 29}
+
+    def _emit_conv(self, P, problems, Cout, Cin, flags, role, engine, teacher=False):
+        """One launch of independent convolutions of equal (Cout, Cin) on one engine (the split-operand engine's
+        workspace is bound by _finish_workspaces)."""
         arr = self._conv_table(problems)
         px = sum(x.shape[0] * x.shape[2] * x.shape[3] for p in problems for x in p[0])
-        wino = self._use_wino(Cout)
-        if not wino and klass in (2, 3, 4, 16):
-            klass = 18
-        if split:
+        klass = 18 if engine == Engine.DIRECT else self.KLASS[("teacher_" if teacher else "") + role, engine]
+        ptrs, sizes = (arr, None, None), ()
+        if engine == Engine.SPLIT:
             nb = K.lib().ssad_conv3x3_split_workspace_bytes(arr, len(arr), Cin)
             self._split_ws_need = max(self._split_ws_need, nb)
-            xa = ya = None
-            if self._amax_on:
-                xa = self._amax_addr(self._amax_measure(P, arr, [list(p[0]) for p in problems], Cin))
-                ya = self._amax_addr(self._amax_block([list(p[1]) for p in problems]))     # folded in by the epilogue
-            idx = P.add(PR.CONV3X3, klass, i=(len(arr), Cout, Cin, flags, 3), l=(nb,), p=(arr, None, None, None, xa, ya),
-                        work=2.0 * 9 * Cout * Cin * px,
-                        keep=[t for p in problems for t in (list(p[0]) + list(p[1] or []) + list(p[2] or []))
-                              ] + [t for p in problems for t in p[3:] if t is not None])
-            self._split_ops.append((P, idx))
-            return idx, arr
-        idx = P.add(PR.CONV3X3, klass, i=(len(arr), Cout, Cin, flags, 2 if (f24 and wino) else int(wino)), p=(arr, None, None),
+            xa = self._amax_addr(self._amax_measure(P, arr, [list(p[0]) for p in problems], Cin))
+            ya = self._amax_addr(self._amax_block([list(p[1]) for p in problems]))     # folded in by the epilogue
+            ptrs, sizes = (arr, None, None, None, xa, ya), (nb,)
+        idx = P.add(PR.CONV3X3, klass, i=(len(arr), Cout, Cin, flags, engine), l=sizes, p=ptrs,
                     work=2.0 * 9 * Cout * Cin * px,
                     keep=[t for p in problems for t in (list(p[0]) + list(p[1] or []) + list(p[2] or []))
                           ] + [t for p in problems for t in p[3:] if t is not None])
+        if engine == Engine.SPLIT:
+            self._split_ops.append((P, idx))
         return idx, arr
+
+    def _emit_group(self, P, probs, role, flags, bind=False):
+        """probs: [(who, layer, problem)], forward convolutions that may share launches: one launch per (Cout, Cin,
+        planned engine), the teacher's own launches first.  bind: the problems read the bound FPN levels."""
+        groups = OrderedDict()
+        for who, layer, prob in probs:
+            cout, cin = (self.teacher if who == "teacher" else self.params)[layer + "_w"].shape[:2]
+            groups.setdefault((cout, cin, self.fwd_engine[who, layer]), []).append((who, prob))
+        for (cout, cin, engine), members in sorted(groups.items(), key=lambda g: any(w != "teacher" for w, _ in g[1])):
+            # The teacher's towers on F(2x4) in a launch of their own, the student's of the same width on F(2x2): the
+            # student's half alone is 19.5 + 4.5 rounds of the 256 CUs where the four towers together were 39 + 9.
+            # These launches have the chip to themselves, so their partial rounds are split.
+            tail = engine == Engine.F22 and any(k[:2] == (cout, cin) and k[2] != engine for k in groups)
+            _, arr = self._emit_conv(P, [p for _, p in members], cout, cin, flags | (K.CONV_SPLIT_TAIL if tail else 0),
+                                     role, engine, teacher=all(w == "teacher" for w, _ in members))
+            if bind:
+                slots = [(w, l) for w, p in members for l in range(len(p[0]))]
+                self._in_slots.extend((arr, k, w, l) for k, (w, l) in enumerate(slots))
 
     def _emit_wgrad(self, P, xs, dys, name, Cout, klass):
         arr = self._conv_table([(xs, None, dys, None, None)])
         # SSAD_SPLIT_CONV bit 32 (default): the >= 128-wide filter gradients on the split-operand engine
-        split = bool(self.split_conv & 32) and Cout >= 128 and self.D >= 64
+        split = bool(self.switches.split_conv & 32) and Cout >= 128 and self.D >= 64
         if split and not K.lib().ssad_conv3x3_wgrad_split_workspace_bytes(arr, len(arr), Cout, self.D):
             split = False           # (a level of 2 GiB or more: the exact engine)
         size_fn = K.lib().ssad_conv3x3_wgrad_split_workspace_bytes if split else K.lib().ssad_conv3x3_wgrad_workspace_bytes
@@ -306,157 +305,65 @@ class DistillHeads(object):
         self._wgrad_ws_need = max(getattr(self, "_wgrad_ws_need", 0), nb)
         px = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
         xa = da = None
-        if split and self._amax_on:     # (on the main stream, before the fork)
+        if split:                       # (on the main stream, before the fork)
             xa = self._amax_addr(self._amax_measure(P, arr, [list(xs)], self.D, 0))
             da = self._amax_addr(self._amax_measure(P, arr, [list(dys)], Cout, 1))
         if self._wstream:
             P.fork(self._wstream)       # behind everything enqueued so far (the producer of dys)
         if split:
             klass = {5: 68, 6: 69}.get(klass, klass)
-        idx = P.add(PR.CONV3X3_WGRAD, klass if self._use_wino(Cout) else 19,
+        idx = P.add(PR.CONV3X3_WGRAD, 19 if self.fwd_engine["student", name] == Engine.DIRECT else klass,
                     i=(len(arr), Cout, self.D, 0, 1 if split else 0), l=(nb,),
                     p=(arr, self.grads[name + "_w"], self.grads[name + "_b"], None, xa, da),
                     work=2.0 * 9 * Cout * self.D * px, keep=list(xs) + list(dys), stream=self._wstream)
         self._wgrad_ops.append(idx)
         return idx, arr
 
-    def _f24_layer(self, name, cout):
-        """Does the TEACHER's layer `name` run on the F(2x4, 3x3) engine?"""
-        if not self.teacher_f24 or cout < 128:
-            return False
-        return "_pred_" in name or self.teacher_f24 >= 2
+    PACK_ORDER = (Engine.SPLIT, Engine.F24, Engine.F22, Engine.DIRECT)
 
-    def _f24_use(self, who, name, cout, cin, which):
-        """Engine of one convolution: who = "teacher" | "student", which = "fwd" | "dgrad" (M = cout / cin)."""
-        if who == "teacher":
-            return which == "fwd" and self._f24_layer(name, cout)
-        m = self.student_f24
-        if which == "dgrad":
-            return bool(m & 1) and cin >= 128
-        if cout < 128:
-            return False
-        return bool(m & 2) if "_pred_" in name else bool(m & 4)
-
-    def _split_use(self, name, cout, cin, which):
-        """Does this convolution run on the split-operand engine?  SSAD_SPLIT_CONV bits: 1 cls_pred forward (both
-        networks), 2 its data gradient, 4 tower forward (both networks: one launch per depth), 8 tower data gradient."""
-        m = self.split_conv
-        if not m or "bbox_pred" in name:
-            return False
-        if "_cls_pred_" in name:
-            return bool(m & (1 if which == "fwd" else 2))
-        return bool(m & (4 if which == "fwd" else 8))
-
-    def _alloc_packed(self, params, want_dgrad, f24=None):
-        """Packed-filter buffers per layer in the layout of the engine that consumes them:
-        -> ({name: (fwd, dgrad)}, wino pack entries, direct pack ops[, F(2x4) pack entries]); f24 = "teacher" |
-        "student": whose layers these are (None: no F(2x4) engine, three results)."""
-        L = K.lib()
-        packed, entries, direct, entries24, entries_sp = {}, [], [], [], []
+    def _alloc_packed(self, params, who):
+        """Packed-filter buffers of who's layers ("student": forward and data gradient, "teacher": forward), each in
+        the layout of the engine planned to read it -> ({layer: (fwd, dgrad or None)}, what _emit_pack needs: here
+        {Engine: pack entries})."""
+        packed, packs = {}, {}
         for tower in ("cls", "bbox"):
             for name in self._layers(tower):
                 w = params[name + "_w"]
                 cout, cin = w.shape[0], w.shape[1]
-                pf = pd = None
-                fw, dw = self._use_wino(cout), self._use_wino(cin)
-                f_sp = bool(f24) and fw and self._split_use(name, cout, cin, "fwd")
-                d_sp = bool(f24) and want_dgrad and dw and self._split_use(name, cout, cin, "dgrad")
-                f_24 = bool(f24) and fw and not f_sp and self._f24_use(f24, name, cout, cin, "fwd")
-                d_24 = bool(f24) and want_dgrad and dw and not d_sp and self._f24_use(f24, name, cout, cin, "dgrad")
-                nf = (L.ssad_conv_split_filter_floats if f_sp else L.ssad_conv_wino24_filter_floats if f_24
-                      else L.ssad_conv_wino_filter_floats if fw else L.ssad_conv_packed_filter_floats)(cout, cin)
-                pf = torch.empty(nf, dtype=torch.float32, device=self.device)
-                if want_dgrad:
-                    nd = (L.ssad_conv_split_filter_floats if d_sp else L.ssad_conv_wino24_filter_floats if d_24
-                          else L.ssad_conv_wino_filter_floats if dw else L.ssad_conv_packed_filter_floats)(cin, cout)
-                    pd = torch.empty(nd, dtype=torch.float32, device=self.device)
+                ef, ed = self.fwd_engine[who, name], self.dgrad_engine[name] if who == "student" else None
+                pf = torch.empty(filter_floats(ef)(cout, cin), dtype=torch.float32, device=self.device)
+                pd = None
+                if ed is not None:
+                    pd = torch.empty(filter_floats(ed)(cin, cout), dtype=torch.float32, device=self.device)
                 packed[name] = (pf, pd)
-                if f_sp or d_sp:
-                    entries_sp.append((w, cout, cin, pf if f_sp else None, pd if d_sp else None))
-                xf, xd = (pf if f_24 else None), (pd if d_24 else None)
-                if xf is not None or xd is not None:
-                    entries24.append((w, cout, cin, xf, xd))
-                wf = pf if (fw and not f_24 and not f_sp) else None
-                wd = pd if (dw and want_dgrad and not d_24 and not d_sp) else None
-                if wf is not None or wd is not None:
-                    entries.append((w, cout, cin, wf, wd))
-                df, dd = (pf if not fw else None), (pd if (not dw and want_dgrad) else None)
-                if df is not None or dd is not None:
-                    direct.append((w, cout, cin, df, dd))
-        if f24:
-            self._entries_split[f24] = entries_sp
-        return (packed, entries, direct, entries24) if f24 else (packed, entries, direct)
+                for e in {ef, ed} - {None}:
+                    packs.setdefault(e, []).append((w, cout, cin, pf if e == ef else None, pd if e == ed else None))
+        return packed, packs
 
-    def _emit_pack(self, P, entries, direct, entries24=(), entries_sp=()):
-        if entries_sp:
-            tab = (K.PackEntry * len(entries_sp))()
-            nbytes = 0
-            for k, (w, cout, cin, pf, pd) in enumerate(entries_sp):
-                tab[k] = K.PackEntry(w.data_ptr(), cout, cin, pf.data_ptr() if pf is not None else 0,
-                                     pd.data_ptr() if pd is not None else 0)
-                nbytes += 4 * (w.numel() + (pf.numel() if pf is not None else 0) + (pd.numel() if pd is not None else 0))
-            P.add(PR.WINO_PACK_FILTERS, 1, i=(len(entries_sp), 3), p=(tab,), work=nbytes,
-                  keep=[t for e in entries_sp for t in e if isinstance(t, torch.Tensor)])
-        if entries24:
-            tab = (K.PackEntry * len(entries24))()
-            nbytes = 0
-            for k, (w, cout, cin, pf, pd) in enumerate(entries24):
-                tab[k] = K.PackEntry(w.data_ptr(), cout, cin, pf.data_ptr() if pf is not None else 0,
-                                     pd.data_ptr() if pd is not None else 0)
-                nbytes += 4 * (w.numel() + (pf.numel() if pf is not None else 0)
-                               + (pd.numel() if pd is not None else 0))
-            P.add(PR.WINO_PACK_FILTERS, 1, i=(len(entries24), 2), p=(tab,), work=nbytes,
-                  keep=[t for e in entries24 for t in e if isinstance(t, torch.Tensor)])
-        if entries:
-            tab = (K.PackEntry * len(entries))()
-            nbytes = 0
-            for k, (w, cout, cin, pf, pd) in enumerate(entries):
-                tab[k] = K.PackEntry(w.data_ptr(), cout, cin, pf.data_ptr() if pf is not None else 0,
-                                     pd.data_ptr() if pd is not None else 0)
-                nbytes += 4 * (w.numel() + (pf.numel() if pf is not None else 0)
-                               + (pd.numel() if pd is not None else 0))
-            P.add(PR.WINO_PACK_FILTERS, 1, i=(len(entries),), p=(tab,), work=nbytes,
-                  keep=[t for e in entries for t in e if isinstance(t, torch.Tensor)])
-        for w, cout, cin, pf, pd in direct:
-            P.add(PR.PACK_FILTER, 1, i=(cout, cin), p=(w, pf, pd),
-                  work=4 * (w.numel() + (pf.numel() if pf is not None else 0)
-                            + (pd.numel() if pd is not None else 0)))
+    def _emit_pack(self, P, packs):
+        emit_packs(P, 1, packs, self.PACK_ORDER)
 
     def _build_programs(self):
-        import os
         # filter gradients on an auxiliary stream beside the data-gradient chain (program.py FORK / JOIN)
         ov = self._overlap_wgrad
         self._wstream = 1 if (os.environ.get("SSAD_OVERLAP_WGRAD", "1") == "1" if ov is None else ov) else 0
         self._wgrad_ops, self._wgrad_ws_need = [], 0
-        # the table of |max| words serves the fp32 split engines (not the fp16-storage subclass)
-        self._amax_on = bool(self.split_conv) and not self.F16
         self.amax = torch.zeros(self.AMAX_WORDS, dtype=torch.int32, device=self.device)
         self._amax_groups, self._amax_next = {}, 0
         self._in_slots = []          # (table, index, which): entries that read the bound inputs
-        self._entries_split = {}
         # filters (the teacher's are frozen: packed by a program of their own, run when they change)
-        if self.F16:
-            self.packed, s_entries, s_direct = self._alloc_packed(self.params, True)
-            s_extra = ()
-        else:
-            self.packed, s_entries, s_direct, s_entries24 = self._alloc_packed(self.params, True, f24="student")
-            s_extra = (s_entries24, self._entries_split.get("student", []))
+        self.packed, s_packs = self._alloc_packed(self.params, "student")
         if self.distill:
-            if self.F16:            # (the fp16 subclass has its own pack layouts and no F(2x4) engine)
-                self.t_packed_pairs, t_entries, t_direct = self._alloc_packed(self.teacher, False)
-                t_extra = ()
-            else:
-                self.t_packed_pairs, t_entries, t_direct, t_entries24 = self._alloc_packed(self.teacher, False, f24="teacher")
-                t_extra = (t_entries24, self._entries_split.get("teacher", []))
+            self.t_packed_pairs, t_packs = self._alloc_packed(self.teacher, "teacher")
             self.t_packed = {k: v[0] for k, v in self.t_packed_pairs.items()}
             T = self.prog_teacher_pack = PR.Program()
-            self._emit_pack(T, t_entries, t_direct, *t_extra)
+            self._emit_pack(T, t_packs)
             T.build()
         P = self.prog = PR.Program()
         P.mark("pack")
-        self._emit_pack(P, s_entries, s_direct, *s_extra)
+        self._emit_pack(P, s_packs)
         P.mark("forward")
-        if self._amax_on:
+        if self.switches.split_conv:      # the table of |max| words serves the split-operand engines
             P.add(PR.FILL, 11, p=(self.amax,), f=(0.0,), l=(self.AMAX_WORDS,), work=4.0 * self.AMAX_WORDS)
         self._emit_forward(P)
         P.mark("losses")
@@ -491,103 +398,32 @@ class DistillHeads(object):
         depth is ONE launch of up to 20 (level, filter) problems: 12 480 equal workgroups fill
         the 256 CUs to 99 % where five separate launches would each leave a partial last wave.
         Teacher cls_pred carries the Sigmoid epilogue (retinanet_heads.py:153-163)."""
-        cfg, D = self.cfg, self.D
-        AC, A4 = self.A * self.C, 4 * self.A
+        cfg = self.cfg
         tx = {"cls": self.t_fpn_in, "bbox": self.t_fpn_in}
         sx = {"cls": self.fpn_in, "bbox": self.fpn_in}
         for i in range(cfg.num_convs):
-            probs, who = [], []
+            probs = []
             for t in ("cls", "bbox"):
                 name = self._layers(t)[i]
                 if self.distill and (t == "cls" or self.teacher_bbox_tower):
                     out = self.t_buf[t][i & 1]
-                    probs.append((tx[t], out, None, self.t_packed_for(name), self.teacher[name + "_b"]))
-                    who.append("teacher")
+                    probs.append(("teacher", name, (tx[t], out, None, self.t_packed_for(name), self.teacher[name + "_b"])))
                     tx[t] = out
                 out = self.act[t][i]
-                probs.append((sx[t], out, None, self.packed[name][0], self.params[name + "_b"]))
-                who.append("student")
+                probs.append(("student", name, (sx[t], out, None, self.packed[name][0], self.params[name + "_b"])))
                 sx[t] = out
-            if self.Dt != D:
-                # a thin student under a full-width teacher: two widths, two launches per depth, each on the engine the
-                # rules below give a launch of its width (split-operand, else F(2x4) from 128 outputs, else F(2x2))
-                for w, dim in (("teacher", self.Dt), ("student", D)):
-                    plist = [p for p, ww in zip(probs, who) if ww == w]
-                    if not plist:
-                        continue
-                    name = self._layers("cls")[i]
-                    if self.split_conv & 4:
-                        _, arr = self._emit_conv(P, plist, dim, dim, K.CONV_RELU, 28, split=True)
-                    elif self._f24_use(w, name, dim, dim, "fwd"):
-                        _, arr = self._emit_conv(P, plist, dim, dim, K.CONV_RELU, 21 if w == "teacher" else 23, f24=True)
-                    else:
-                        _, arr = self._emit_conv(P, plist, dim, dim, K.CONV_RELU, 2)
-                    if i == 0:
-                        k = 0
-                        for (xs, _, _, _, _) in plist:
-                            for l in range(len(xs)):
-                                self._in_slots.append((arr, k, w, l))
-                                k += 1
-                continue
-            if self.split_conv & 4:
-                # every tower of this depth on the split-operand engine, one launch (class 28)
-                _, arr = self._emit_conv(P, probs, D, D, K.CONV_RELU, 28, split=True)
-                if i == 0:
-                    k = 0
-                    for (xs, _, _, _, _), w in zip(probs, who):
-                        for l in range(len(xs)):
-                            self._in_slots.append((arr, k, w, l))
-                            k += 1
-                continue
-            if self.student_f24 & 4 and (not self.distill or self._f24_layer(self._layers("cls")[i], D)):
-                # every tower of this depth on the F(2x4) engine, one launch (class 23)
-                _, arr = self._emit_conv(P, probs, D, D, K.CONV_RELU, 23, f24=True)
-                if i == 0:
-                    k = 0
-                    for (xs, _, _, _, _), w in zip(probs, who):
-                        for l in range(len(xs)):
-                            self._in_slots.append((arr, k, w, l))
-                            k += 1
-                continue
-            if self.distill and self._f24_layer(self._layers("cls")[i], D):
-                # the teacher's towers on the F(2x4) engine: a launch of their own (class 21), the student's on F(2x2)
-                tp = [p for p, w in zip(probs, who) if w == "teacher"]
-                sp_ = [p for p, w in zip(probs, who) if w == "student"]
-                _, arr_t = self._emit_conv(P, tp, D, D, K.CONV_RELU, 21, f24=True)
-                # (the student's half alone is 19.5 + 4.5 rounds of the 256 CUs where the four towers together were
-                # 39 + 9: these launches have the chip to themselves, so their partial rounds are split)
-                _, arr_s = self._emit_conv(P, sp_, D, D, K.CONV_RELU | K.CONV_SPLIT_TAIL, 2)
-                if i == 0:
-                    for arr, plist, w in ((arr_t, tp, "teacher"), (arr_s, sp_, "student")):
-                        k = 0
-                        for (xs, _, _, _, _) in plist:
-                            for l in range(len(xs)):
-                                self._in_slots.append((arr, k, w, l))
-                                k += 1
-                continue
-            _, arr = self._emit_conv(P, probs, D, D, K.CONV_RELU, 2)
-            if i == 0:
-                k = 0
-                for (xs, _, _, _, _), w in zip(probs, who):
-                    for l in range(len(xs)):
-                        self._in_slots.append((arr, k, w, l))
-                        k += 1
+            # (a thin student under a full-width teacher: two widths, so two launches per depth)
+            self._emit_group(P, probs, "tower", K.CONV_RELU, bind=i == 0)
         cp, bp = self._layers("cls")[-1], self._layers("bbox")[-1]
-        sp = self._split_use(cp, AC, D, "fwd")
         if self.distill:
-            f24 = self._f24_layer(cp, AC)
-            self._emit_conv(P, [(tx["cls"], self.t_prob, None, self.t_packed_for(cp), self.teacher[cp + "_b"])],
-                            AC, self.Dt, K.CONV_SIGMOID, 25 if sp else 20 if f24 else 3, f24=f24, split=sp)
-        f24 = self._f24_use("student", cp, AC, D, "fwd")
-        self._emit_conv(P, [(sx["cls"], self.cls_logits, None, self.packed[cp][0], self.params[cp + "_b"])],
-                        AC, D, 0, 26 if sp else 22 if f24 else 3, f24=f24, split=sp)
-        probs = [(sx["bbox"], self.bbox_pred, None, self.packed[bp][0], self.params[bp + "_b"])]
-        if self.teacher_bbox_tower and self.Dt != D:
-            self._emit_conv(P, [(tx["bbox"], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"])],
-                            A4, self.Dt, 0, 4)
-        elif self.teacher_bbox_tower:
-            probs.append((tx["bbox"], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"]))
-        self._emit_conv(P, probs, A4, D, 0, 4)
+            self._emit_group(P, [("teacher", cp, (tx["cls"], self.t_prob, None, self.t_packed_for(cp), self.teacher[cp + "_b"]))],
+                             "cls_pred", K.CONV_SIGMOID)
+        self._emit_group(P, [("student", cp, (sx["cls"], self.cls_logits, None, self.packed[cp][0], self.params[cp + "_b"]))],
+                         "cls_pred", 0)
+        probs = [("student", bp, (sx["bbox"], self.bbox_pred, None, self.packed[bp][0], self.params[bp + "_b"]))]
+        if self.teacher_bbox_tower:
+            probs.append(("teacher", bp, (tx["bbox"], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"])))
+        self._emit_group(P, probs, "bbox_pred", 0)
 
     def t_packed_for(self, name):
         return self.t_packed[name]
@@ -688,10 +524,8 @@ class DistillHeads(object):
             Cout = self.params[name + "_b"].numel()
             self._emit_wgrad(P, x_in, dy[t], name, Cout, klass_w)
             out = self.dbuf[t][nl]
-            sp = self._split_use(name, Cout, D, "dgrad")
-            f24 = self._f24_use("student", name, Cout, D, "dgrad")
             self._emit_conv(P, [(dy[t], out, x_in, self.packed[name][1], None)], D, Cout, K.CONV_MASK_AUX,
-                            27 if sp else 24 if f24 else 16, f24=f24, split=sp)
+                            "pred_dgrad", self.dgrad_engine[name])
             dy[t] = out
         for li in range(nl - 1, -1, -1):
             probs = []
@@ -705,9 +539,8 @@ class DistillHeads(object):
                 out = self.dbuf[t][li] if li > 0 else self.d_fpn[t]
                 probs.append((dy[t], out, x_in if li > 0 else None, self.packed[name][1], None))
                 dy[t] = out
-            sp = self._split_use(name, D, D, "dgrad")
-            f24 = self._f24_use("student", name, D, D, "dgrad")
-            self._emit_conv(P, probs, D, D, K.CONV_MASK_AUX if li > 0 else 0, 29 if sp else 24 if f24 else 16, f24=f24, split=sp)
+            self._emit_conv(P, probs, D, D, K.CONV_MASK_AUX if li > 0 else 0, "tower_dgrad",
+                            same_engine(self.dgrad_engine[self._layers(t)[li]] for t in ("cls", "bbox")))
             if li == nl // 2:
                 P.mark("backward_late_done")
         if "backward_late_done" not in P.marks:
@@ -936,8 +769,9 @@ class DistillHeadsF16(DistillHeads):
     def loss_scale(self):
         return float(self.ls_state[0])
 
-    def _alloc_packed(self, params, want_dgrad):
-        packed, ops = {}, []
+    def _alloc_packed(self, params, who):
+        """-> ({layer: (fwd, dgrad or None)}, what _emit_pack needs: here the list of ssad_f16_pack_entry fields)"""
+        packed, ops, want_dgrad = {}, [], who == "student"
         for tower in ("cls", "bbox"):
             for name in self._layers(tower):
                 w = params[name + "_w"]
@@ -947,9 +781,9 @@ class DistillHeadsF16(DistillHeads):
                 wd = torch.empty(n, dtype=torch.float16, device=self.device) if want_dgrad else None
                 packed[name] = (wf, wd)
                 ops.append((w, M, Cc, wf, wd))
-        return packed, ops, []
+        return packed, ops
 
-    def _emit_pack(self, P, entries, direct):
+    def _emit_pack(self, P, entries):
         """All of a network's filters in one launch (ssad_f16_pack_filters)."""
         if not entries:
             return

@@ -1,0 +1,269 @@
+#!/usr/bin/env python3
+"""Fingerprints of the native programs over a matrix of engine switches.
+
+A program is the list of launch records a pipeline builds once (program.Program); which engine a convolution runs
+on, which layout its filter is packed in and which timing class it is booked under are all fields of those
+records and of the tables they point to.  This script builds every configuration below over CPU tensors
+(addresses only, nothing is launched), writes each program down with its addresses made canonical, and hashes the
+listing.  tests/test_program_fingerprints.py rebuilds the configurations and compares: a change that is meant to
+leave the programs alone (a refactoring of the engine rules) must leave every hash alone.
+
+It uses only Program.ops / .keep / .marks and the pipelines' constructors, so it runs against any commit:
+
+    python tests/golden/make_program_fingerprints.py --write       # tests/golden/program_fingerprints.json
+    python tests/golden/make_program_fingerprints.py --dump NAME   # one configuration's readable listing
+    python tests/golden/make_program_fingerprints.py --list
+
+A mismatch is located by diffing `--dump NAME` of the two commits.
+
+Canonical addresses: a ctypes table of Program.keep is T<ordinal of first appearance>(+offset); an address inside
+the storage of a tensor of Program.keep is S<ordinal of first appearance of that storage>+<byte offset>; any other
+address is U<ordinal of first appearance>.  The contents of a table are listed, field by field, where it first
+appears; its c_void_p fields are canonical in the same way.  A storage's size is listed where it first appears (a
+packed filter's size is its layout's).
+"""
+import argparse
+import bisect
+import contextlib
+import ctypes as C
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+OUT = os.path.join(HERE, "program_fingerprints.json")
+
+SWITCHES = ("SSAD_SPLIT_CONV", "SSAD_STUDENT_F24", "SSAD_TEACHER_F24", "SSAD_CONV_ENGINE", "SSAD_STRIDED_3X3")
+SHAPES = [(10, 14), (5, 7)]
+PROGRAMS = ("prog", "prog_teacher_pack", "prog_distill_only", "prep")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the listing
+# ---------------------------------------------------------------------------------------------------------------
+class _Canon(object):
+    """Address -> canonical name, over every program of one configuration."""
+
+    def __init__(self, programs):
+        import torch
+        self.tables, self.storages = {}, {}            # start address -> (size, object)
+        for P in programs:
+            for v in P.keep:
+                if isinstance(v, torch.Tensor):
+                    st = v.untyped_storage()
+                    if st.nbytes() > 0:
+                        self.storages[st.data_ptr()] = (st.nbytes(), None)
+                elif isinstance(v, (C.Structure, C.Array, C._SimpleCData)):
+                    self.tables[C.addressof(v)] = (C.sizeof(v), v)
+        self.t_starts, self.s_starts = sorted(self.tables), sorted(self.storages)
+        self.t_ord, self.s_ord, self.u_ord = {}, {}, {}
+        self.pending = []                              # tables named but not yet listed
+        self.new_storages = []                         # storages named but their sizes not yet listed
+
+    @staticmethod
+    def _find(starts, ranges, a):
+        k = bisect.bisect_right(starts, a) - 1
+        if k >= 0 and a < starts[k] + ranges[starts[k]][0]:
+            return starts[k]
+        return None
+
+    def name(self, a):
+        if not a:
+            return "0"
+        t = self._find(self.t_starts, self.tables, a)
+        if t is not None:
+            if t not in self.t_ord:
+                self.t_ord[t] = len(self.t_ord)
+                self.pending.append(t)
+            return "T%d" % self.t_ord[t] + ("+%d" % (a - t) if a != t else "")
+        s = self._find(self.s_starts, self.storages, a)
+        if s is not None:
+            if s not in self.s_ord:
+                self.s_ord[s] = len(self.s_ord)
+                self.new_storages.append(s)
+            return "S%d+%d" % (self.s_ord[s], a - s)
+        return "U%d" % self.u_ord.setdefault(a, len(self.u_ord))
+
+    def value(self, v):
+        """One ctypes value, written down."""
+        if isinstance(v, C.c_void_p):
+            return self.name(v.value)
+        if isinstance(v, C.Array):
+            if issubclass(v._type_, C.c_void_p):
+                return "[" + " ".join(self.name(x) for x in v) + "]"
+            if issubclass(v._type_, (C.Structure, C.Array)):
+                return "[" + " ".join(self.value(x) for x in v) + "]"
+            return "[" + " ".join(repr(x) for x in v) + "]"
+        if isinstance(v, C.Structure):
+            parts = []
+            for fname, ftype in v._fields_:
+                x = getattr(v, fname)
+                if issubclass(ftype, C.c_void_p):
+                    parts.append("%s=%s" % (fname, self.name(x)))
+                elif issubclass(ftype, (C.Structure, C.Array)):
+                    parts.append("%s=%s" % (fname, self.value(x)))
+                else:
+                    parts.append("%s=%r" % (fname, x))
+            return "{" + " ".join(parts) + "}"
+        if isinstance(v, C._SimpleCData):
+            return repr(v.value)
+        return repr(v)
+
+    def drain(self, lines):
+        """List the tables named since the last call (a table may name further tables)."""
+        while self.pending:
+            t = self.pending.pop(0)
+            v = self.tables[t][1]
+            head = "  T%d %s" % (self.t_ord[t], type(v).__name__)
+            if isinstance(v, C.Array) and issubclass(v._type_, (C.Structure, C.Array)):
+                lines.append(head)
+                for k, x in enumerate(v):
+                    lines.append("    [%d] %s" % (k, self.value(x)))
+            else:
+                lines.append(head + " " + self.value(v))
+        for s in self.new_storages:
+            lines.append("  S%d %d bytes" % (self.s_ord[s], self.storages[s][0]))
+        del self.new_storages[:]
+
+
+def listing(objects):
+    """Readable listing of every program of the objects of one configuration -> (lines, op count)."""
+    named = []
+    for k, obj in enumerate(objects):
+        for attr in PROGRAMS:
+            P = getattr(obj, attr, None)
+            if P is not None:
+                named.append(("%d.%s" % (k, attr), P))
+    canon = _Canon([P for _, P in named])
+    lines, nops = [], 0
+    for title, P in named:
+        lines.append("program %s: %d ops, marks %s" % (title, len(P.ops), " ".join("%s=%d" % kv for kv in P.marks.items())))
+        nops += len(P.ops)
+        for k, o in enumerate(P.ops):
+            lines.append("%4d code=%d klass=%d stream=%d i=%s f=%s l=%s work=%r p=%s" % (
+                k, o.code, o.klass, o.stream, list(o.i), [repr(x) for x in o.f], list(o.l), o.work,
+                [canon.name(a) for a in o.p]))
+            canon.drain(lines)
+    return lines, nops
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the configurations
+# ---------------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _env(**env):
+    saved = {k: os.environ.get(k) for k in SWITCHES}
+    for k in SWITCHES:
+        os.environ.pop(k, None)
+    for k, v in env.items():
+        os.environ[k] = str(v)
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def _matrix():
+    return [dict(SSAD_SPLIT_CONV=s, SSAD_STUDENT_F24=f, SSAD_TEACHER_F24=t)
+            for s in (0, 3, 15, 47, 511) for f in (0, 1, 3, 7, 15) for t in (0, 1, 2)]
+
+
+def _tag(env):
+    return "split%d_sf%d_tf%d" % (env["SSAD_SPLIT_CONV"], env["SSAD_STUDENT_F24"], env["SSAD_TEACHER_F24"])
+
+
+def configurations():
+    """[(name, environment, builder -> list of pipeline objects)]"""
+    from ssad_amd.backbone_f16 import NativeResNetFPNF16
+    from ssad_amd.backbone_pipeline import NativeResNetFPN
+    from ssad_amd.head_pipeline import DistillHeads, DistillHeadsF16
+    from ssad_amd.modeling.retinanet_heads import HeadConfig
+
+    def heads(cls=DistillHeads, cfg=None, **kw):
+        return lambda: [cls(cfg or HeadConfig(num_gpus=1), N=1, shapes=SHAPES, device="cpu", **kw)]
+
+    def backbone(arch="r50", **kw):
+        return lambda: [NativeResNetFPN(arch, 1, (128, 128), "cpu", **kw)]
+
+    def f16_pair():
+        shapes = [(16, 16), (8, 8), (4, 4), (2, 2), (1, 1)]
+        h = DistillHeadsF16(HeadConfig(num_gpus=1), N=1, shapes=shapes, device="cpu", blocked_io=True)
+        st = NativeResNetFPNF16("r50", 1, (128, 128), "cpu", train=True,
+                                heads_io=dict(fpn_out=h.in_blk["student"], inv_scale=h.ls_state[1:2],
+                                              d_fpn_in=(h.dbuf["cls"][0], h.dbuf["bbox"][0])),
+                                skip_flag=h.ls_counters)
+        te = NativeResNetFPNF16("x101-64x4d", 1, (128, 128), "cpu", train=False,
+                                heads_io=dict(fpn_out=h.in_blk["teacher"]))
+        return [h, st, te]
+
+    out = []
+    for env in _matrix():
+        for distill in (True, False):
+            out.append(("heads_%s_%s" % (_tag(env), "distill" if distill else "plain"), env, heads(distill=distill)))
+    out.append(("heads_direct", dict(SSAD_CONV_ENGINE="direct"), heads()))
+    out.append(("heads_no_teacher_bbox_tower", {}, heads(teacher_bbox_tower=False)))
+    out.append(("heads_no_overlap_wgrad", {}, heads(overlap_wgrad=False)))
+    for dim in (128, 64):
+        for tag, env in (("default", {}), ("split0", dict(SSAD_SPLIT_CONV=0))):
+            out.append(("heads_thin%d_%s" % (dim, tag), env,
+                        heads(cfg=HeadConfig(num_gpus=1, fpn_dim=dim), teacher_fpn_dim=256)))
+    out.append(("heads_f16", {}, heads(cls=DistillHeadsF16)))
+    for env in _matrix()[::7]:
+        for train in (True, False):
+            out.append(("r50_%s_%s" % (_tag(env), "train" if train else "frozen"), env, backbone(train=train)))
+    for ratio in (0.5, 0.25):
+        out.append(("r50_ratio%d_train" % int(ratio * 100), {}, backbone(train=True, channel_ratio=ratio)))
+    out.append(("r101_frozen", {}, backbone("r101", train=False)))
+    out.append(("x101_64x4d_frozen", {}, backbone("x101-64x4d", train=False)))
+    out.append(("r50_strided_winograd_train", dict(SSAD_STRIDED_3X3="winograd"), backbone(train=True)))
+    out.append(("f16_pair", {}, f16_pair))
+    return out
+
+
+def fingerprint(env, build):
+    """-> [sha256 of the listing, op count]"""
+    with _env(**env):
+        lines, nops = listing(build())
+    return [hashlib.sha256("\n".join(lines).encode()).hexdigest(), nops]
+
+
+def fingerprints():
+    return {name: fingerprint(env, build) for name, env, build in configurations()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--write", action="store_true", help="write %s" % os.path.relpath(OUT, ROOT))
+    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--dump", metavar="NAME", help="print one configuration's listing")
+    ap.add_argument("--list", action="store_true", help="print the configurations' names")
+    args = ap.parse_args()
+    if args.list:
+        print("\n".join(name for name, _, _ in configurations()))
+        return
+    if args.dump:
+        for name, env, build in configurations():
+            if name == args.dump:
+                with _env(**env):
+                    print("\n".join(listing(build())[0]))
+                return
+        raise SystemExit("no configuration %r (--list)" % args.dump)
+    fp = fingerprints()
+    if args.write:
+        commit = subprocess.check_output(["git", "rev-parse", "HEAD"], cwd=ROOT).decode().strip()
+        with open(args.out, "w") as f:
+            json.dump({"parent": commit, "configurations": fp}, f, indent=0, sort_keys=True)
+            f.write("\n")
+    print("%d configurations, %d distinct fingerprints" % (len(fp), len({v[0] for v in fp.values()})))
+
+
+if __name__ == "__main__":
+    main()
