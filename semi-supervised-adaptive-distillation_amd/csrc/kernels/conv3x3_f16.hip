@@ -334,6 +334,15 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_f16_kernel(const F16Level
   STAMP(3);
 }
 
+// x * scale as a value of its own.  Left to the compiler, the product and its conversion to fp16 become ONE
+// v_fma_mixlo_f16 x, scale, +0 -- and the +0 addend turns a product of -0 into +0 (the sign of a zero was lost in
+// every pack and unblock); the empty statement keeps v_mul_f32 and v_cvt_f16_f32 apart.
+__device__ __forceinline__ float scaled(float x, float scale) {
+  float v = x * scale;
+  asm("" : "+v"(v));
+  return v;
+}
+
 // NCHW fp32 -> blocked fp16 (round to nearest even), one thread per 16-byte slot
 template <typename T>   // T = float (the subnet pipeline) or _Float16 (float16 blobs of the operator surface)
 __global__ __launch_bounds__(kThreads) void f16_pack_kernel(const T* __restrict__ x,
@@ -351,7 +360,7 @@ __global__ __launch_bounds__(kThreads) void f16_pack_kernel(const T* __restrict_
     half8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      o[e] = cb * 8 + e < C ? (_Float16)((float)src[e * plane] * scale) : (_Float16)0.0f;
+      o[e] = cb * 8 + e < C ? (_Float16)scaled((float)src[e * plane], scale) : (_Float16)0.0f;
     xb[i] = __builtin_bit_cast(uint4, o);
   }
 }
@@ -373,7 +382,7 @@ __global__ __launch_bounds__(kThreads) void f16_unpack_kernel(const uint4* __res
     T* dst = x + ((ncb / CB) * C + cb * 8) * plane + px;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      if (cb * 8 + e < C) dst[e * plane] = (T)((float)v[e] * scale);
+      if (cb * 8 + e < C) dst[e * plane] = (T)scaled((float)v[e], scale);
   }
 }
 

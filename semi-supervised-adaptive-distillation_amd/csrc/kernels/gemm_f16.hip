@@ -378,11 +378,15 @@ __global__ __launch_bounds__(kThreads) void ew_f16_kernel(const EwF16 p) {
         const int Wa = p.W * 2;
         const uint4* s = p.a + (ncb * p.H * 2 + 2LL * y) * Wa + 2 * x;
         const half8 a0 = as_half8(s[0]), a1 = as_half8(s[1]), a2 = as_half8(s[Wa]), a3 = as_half8(s[Wa + 1]);
+        // + the level's own gradient (the lateral Sum's other input), added in fp32: ONE rounding of the stored sum
+        const half8 own = p.b ? as_half8(p.b[i]) : as_half8(zero);
         half8 o;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (_Float16)(((float)a0[e] + (float)a1[e]) + ((float)a2[e] + (float)a3[e]));
+        for (int e = 0; e < 8; ++e) {
+          const float s = ((float)a0[e] + (float)a1[e]) + ((float)a2[e] + (float)a3[e]);
+          o[e] = (_Float16)(p.b ? s + (float)own[e] : s);
+        }
         v = __builtin_bit_cast(uint4, o);
-        if (p.b) v = h8_add(v, p.b[i]);     // + the level's own gradient (the lateral Sum's other input)
         break;
       }
       case EW_SUM2:

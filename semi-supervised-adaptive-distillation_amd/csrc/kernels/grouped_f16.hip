@@ -18,6 +18,11 @@
 //     8 blocks lands in LDS by LDS-DMA (out-of-image lanes at an out-of-range offset = zero
 //     padding); 23 KiB per workgroup, six resident per CU keep ~140 KiB in flight;
 //   * the packed filter of a wave's super-group stays in registers (20 / 36 VGPRs);
+//   * groups of 4 and 8 share a super-group's block-diagonal operand, and 0 x NaN = NaN: so that a non-finite input
+//     stays inside its group, a tile whose accumulators are not all finite is recomputed with the instruction
+//     issued once per group of the super-group (NG = 4 / 2), the B operand of the other groups' channels read from a
+//     zeroed LDS region, and a lane keeps the accumulator of the group its four output rows belong to.  Finite data
+//     never takes that path and runs the instructions it ran before;
 //   * epilogue: bias (the folded AffineChannel) + ReLU, 8-byte stores.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -44,6 +49,7 @@ constexpr int NB = 8;                        // channel blocks per workgroup (64
 constexpr int SLOTS = NB * HR * HC;          // 1440
 constexpr int PIECES = (SLOTS + 63) / 64;    // 23
 constexpr unsigned kOob = 0x80000000u;
+constexpr int ZB = PIECES * 64;              // first slot of the zeroed region: TR * HC slots, one per row offset of a read
 
 struct GroupedF16 {
   const uint4* x;        // blocked fp16 [N][C/8][H][W]
@@ -58,10 +64,14 @@ struct GroupedF16 {
 __device__ __forceinline__ half8 as_half8(const uint4& v) { return __builtin_bit_cast(half8, v); }
 
 // WIDE = false: groups of <= 16 channels (MF = 5 tap pairs); true: groups of 32 (MF = 9 taps)
-template <bool WIDE>
-__global__ __launch_bounds__(kThreads) void grouped_f16_kernel(const GroupedF16 p) {
+// NG: groups inside a 16-channel super-group (1 for groups of 16 and 32, 2 for groups of 8, 4 for groups of 4)
+// (NG > 1 keeps a tile's eight accumulators; six waves per SIMD -- the six workgroups a CU's LDS holds -- bound the
+// registers the scheduler may spend on hoisting the LDS reads of all eight row segments)
+template <bool WIDE, int NG>
+__global__ __launch_bounds__(kThreads, NG > 1 ? 6 : 1) void grouped_f16_kernel(const GroupedF16 p) {
   constexpr int MF = WIDE ? 9 : 5;
-  __shared__ uint4 lds[PIECES * 64];
+  static_assert(!WIDE || NG == 1, "a group of 32 is two operands wide");
+  __shared__ uint4 lds[NG > 1 ? ZB + TR * HC : PIECES * 64];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i16 = lane & 15, g4 = lane >> 4;
@@ -107,6 +117,9 @@ __global__ __launch_bounds__(kThreads) void grouped_f16_kernel(const GroupedF16 
     const int blk = WIDE ? 4 * (wave >> 1) + g4 : 2 * wave + (g4 & 1);
     boff[mf] = (blk * HR + tap / 3) * HC + i16 + tap % 3;
   }
+  if (NG > 1) {
+    for (int i = tid; i < TR * HC; i += kThreads) lds[ZB + i] = make_uint4(0, 0, 0, 0);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -117,14 +130,16 @@ __global__ __launch_bounds__(kThreads) void grouped_f16_kernel(const GroupedF16 
   const __amdgpu_buffer_rsrc_t yrs = uniform_rsrc(p.y, (unsigned)((long long)p.N * CB * plane * 16));
   const int gx = x0 + i16;
   const int ocb = (oc >> 3);                               // output block of this lane
-#pragma unroll
-  for (int r = 0; r < TR; ++r) {
+  auto fast = [&](int r) {
     float4v acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int mf = 0; mf < MF; ++mf) {
       const half8 b = as_half8(lds[boff[mf] + r * HC]);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mf], b, acc, 0, 0, 0);
     }
+    return acc;
+  };
+  auto store = [&](int r, float4v acc) {
     acc += bq;
     half4 o;
 #pragma unroll
@@ -138,7 +153,56 @@ __global__ __launch_bounds__(kThreads) void grouped_f16_kernel(const GroupedF16 
                             ? (unsigned)((((long long)n * CB + ocb) * plane + gy * p.W + gx) * 16 + 8 * (g4 & 1))
                             : kOob;
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, o), yrs, vo, 0, 0);
+  };
+  if (NG == 1) {
+#pragma unroll
+    for (int r = 0; r < TR; ++r) store(r, fast(r));
+    return;
   }
+  // Several groups in the operand: a non-finite B value makes EVERY row of its instruction non-finite (0 x NaN), so
+  // all-finite accumulators prove that no such value took part and the sums stand as they are: the tile's eight row
+  // segments are computed as before, then tested ONCE (x * 0 is NaN exactly when x is not finite; a test per row
+  // segment put a branch between the segments and cost 0.15 ms of config 5's step).  Otherwise -- wave-uniform, and
+  // rare: an overflowing activation -- the tile is recomputed group by group.
+  float4v accs[TR];
+#pragma unroll
+  for (int r = 0; r < TR; ++r) accs[r] = fast(r);
+  float nf = 0.0f;
+#pragma unroll
+  for (int r = 0; r < TR; ++r)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) nf = __builtin_fmaf(accs[r][e], 0.0f, nf);
+  if (__builtin_amdgcn_ballot_w64(!(nf == 0.0f)) != 0) {
+    // group q of the super-group: its channels are block q (NG = 2) or half q & 1 of block q >> 1 (NG = 4); a lane
+    // holding another block reads zeros, and with NG = 4 the other half of the slot is a zero in registers
+    const uint2* lds8 = reinterpret_cast<const uint2*>(lds);
+#pragma unroll 1
+    for (int r = 0; r < TR; ++r) {                            // (loops, not unrolled: the rare path costs no registers)
+      float4v acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+      for (int q = 0; q < NG; ++q) {
+        const bool keep = (g4 & 1) == (NG == 2 ? q : q >> 1);
+        float4v aq = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf) {
+          const int slot = (keep ? boff[mf] : ZB) + r * HC;
+          half8 b;
+          if (NG == 2) {
+            b = as_half8(lds[slot]);
+          } else {
+            const uint2 v = lds8[2 * slot + (q & 1)];
+            b = as_half8((q & 1) ? make_uint4(0, 0, v.x, v.y) : make_uint4(v.x, v.y, 0, 0));
+          }
+          aq = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mf], b, aq, 0, 0, 0);
+        }
+        if ((NG == 2 ? g4 >> 1 : g4) == q) acc = aq;          // rows 4 g4 .. 4 g4 + 3 belong to group q
+      }
+      store(r, acc);
+    }
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < TR; ++r) store(r, accs[r]);
 }
 
 // w [C][cg][3][3] fp32 -> lane-order operands [C/16][MF][64][8] fp16 (see the kernel's header)
@@ -208,8 +272,11 @@ int ssad_grouped_conv3x3_f16(const void* x_blocked, const void* packed, const fl
   p.relu = relu;
   const long long wgs = (long long)N * p.tiles_x * p.tiles_y * p.slabs;
   if (wgs >= (1LL << 31)) return SSAD_E_BADARG;
-  if (cg > 16) hipLaunchKernelGGL(grouped_f16_kernel<true>, dim3((unsigned)wgs), dim3(kThreads), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(grouped_f16_kernel<false>, dim3((unsigned)wgs), dim3(kThreads), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)wgs), block(kThreads);
+  if (cg > 16) hipLaunchKernelGGL((grouped_f16_kernel<true, 1>), grid, block, 0, (hipStream_t)stream, p);
+  else if (cg == 16) hipLaunchKernelGGL((grouped_f16_kernel<false, 1>), grid, block, 0, (hipStream_t)stream, p);
+  else if (cg == 8) hipLaunchKernelGGL((grouped_f16_kernel<false, 2>), grid, block, 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((grouped_f16_kernel<false, 4>), grid, block, 0, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }
 

@@ -9,14 +9,20 @@ output and workspace of a launch.  After the launch `check()` asserts that
     after the last) still holds the sentinel;
   * every view that was taken with `data` and is not named in `modified` is bit-identical to its host copy
     (operands are frozen);
-  * no output (a 4-byte-element view taken without `data`) still holds a sentinel word, except where the caller says
-    the reference has a NaN.
+  * no output (a view taken without `data`, of 4-byte elements or of 2-byte elements, a byte length that is a multiple
+    of 4 and a 4-byte-aligned start) still holds a sentinel word, except where the caller says the reference has a NaN.
 
 An overrun longer than a guard lands in a neighbouring view; that is still caught, by the frozen-operand check or by
 the test's comparison with its oracle.
 
 The sentinel 0x7FC0A5A5 is a quiet NaN with a recognisable payload.  It is written and compared as a bit pattern
 (int32 / uint8 views) only: a float fill or a float comparison may canonicalise the payload, and NaN != NaN.
+
+fp16 outputs.  In memory the sentinel word is the two halves 0xA5A5, 0x7FC0: -0.02205 and a NaN.  A fully written,
+finite fp16 output cannot contain that pair, so a 2-byte output is searched through its int32 view as well (every
+blocked tensor is a multiple of 16 bytes); a `nan_ok` mask given per fp16 element is reduced to one flag per word, and
+a word is excused only if the reference has a NaN in either of its halves.  Unwritten padding inside an fp16 pack
+therefore holds a NaN in every odd half: a kernel that multiplies padding into a result still fails its comparison.
 """
 import numpy as np
 import torch
@@ -147,17 +153,24 @@ class Arena:
                     raise AssertionError("frozen operand %r modified: %d dirty word(s), the first at byte %d of the view"
                                          % (v.name, len(np.unique(diff // 4)), int(diff[0])))
         for v in self.views:
-            if v.kind != "output" or v.tensor.element_size() != 4:
+            item = v.tensor.element_size()
+            if v.kind != "output" or not (item == 4 or (item == 2 and v.nbytes % 4 == 0 and v.off % 4 == 0)):
                 continue
-            left = (v.tensor.view(torch.int32) == SENTINEL).cpu().numpy()
             ok = (nan_ok or {}).get(v.name)
             if ok is True:
                 continue
-            if ok is not None:
-                left &= ~np.asarray(ok, bool).reshape(left.shape)
+            if item == 4:
+                left = (v.tensor.view(torch.int32) == SENTINEL).cpu().numpy()
+                if ok is not None:
+                    left &= ~np.asarray(ok, bool).reshape(left.shape)
+            else:                                  # words of two halves, in memory order
+                left = (v.tensor.reshape(-1).view(torch.int32) == SENTINEL).cpu().numpy()
+                if ok is not None:
+                    left &= ~np.asarray(ok, bool).reshape(-1, 2).any(axis=1)
             if left.any():
                 first = int(np.flatnonzero(left)[0])
                 raise AssertionError("output %r not written completely: %d word(s) still hold the sentinel, the first at "
                                      "byte %d of the view (element %s)"
-                                     % (v.name, int(left.sum()), 4 * first, np.unravel_index(first, left.shape)))
+                                     % (v.name, int(left.sum()), 4 * first,
+                                        tuple(int(i) for i in np.unravel_index(first, left.shape))))
         return True

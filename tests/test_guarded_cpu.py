@@ -117,5 +117,62 @@ def test_output_left_unwritten_is_reported_unless_the_reference_has_a_nan_there(
         a.check(modified=("nope",))
 
 
+def fresh16():
+    rng = np.random.default_rng(1)
+    a = Arena(Arena.bytes_for(2 * 48, 2 * 48, 2 * 3), device="cpu")
+    x = a.take((2, 3, 8), torch.float16, "x", data=rng.standard_normal((2, 3, 8)).astype(np.float16))
+    y = a.take((2, 3, 8), torch.float16, "y")
+    return a, x, y
+
+
+def test_sentinel_word_as_two_halves():
+    a, x, y = fresh16()
+    h = y.reshape(-1).numpy().view(np.uint16)
+    assert h[0] == 0xA5A5 and h[1] == 0x7FC0                       # memory order: -0.02205, then a NaN
+    v = h[:2].view(np.float16)
+    assert abs(float(v[0]) + 0.02205) < 1e-5 and np.isnan(v[1])
+
+
+def test_unwritten_word_in_an_fp16_output_is_reported():
+    a, x, y = fresh16()
+    y.copy_(x)
+    assert a.check()                                               # fully written: passes
+    a, x, y = fresh16()
+    y.copy_(x)
+    y.reshape(-1).view(torch.int32)[5] = SENTINEL                  # halves 10, 11 left as they were
+    with pytest.raises(AssertionError, match=r"output 'y' not written completely: 1 word\(s\).*byte 20"):
+        a.check()
+    # one written half of a word is enough for the word to count as written
+    a, x, y = fresh16()
+    y.copy_(x)
+    y.reshape(-1).view(torch.int32)[5] = SENTINEL
+    y.reshape(-1)[11] = 1.0
+    assert a.check()
+
+
+def test_nan_ok_for_an_fp16_output_is_per_half_reduced_to_words():
+    a, x, y = fresh16()
+    y.copy_(x)
+    y.reshape(-1).view(torch.int32)[5] = SENTINEL
+    y.reshape(-1).view(torch.int32)[9] = SENTINEL
+    ok = np.zeros((2, 3, 8), bool)
+    ok.reshape(-1)[10] = True                                      # the reference is NaN in the even half of word 5
+    with pytest.raises(AssertionError, match=r"1 word\(s\).*byte 36"):
+        a.check(nan_ok={"y": ok})
+    ok.reshape(-1)[19] = True                                      # ... and in the odd half of word 9
+    assert a.check(nan_ok={"y": ok})
+    ok[:] = False
+    ok.reshape(-1)[12] = True                                      # a NaN next door excuses nothing
+    with pytest.raises(AssertionError, match=r"2 word\(s\)"):
+        a.check(nan_ok={"y": ok})
+    assert a.check(nan_ok={"y": True})
+
+
+def test_fp16_output_of_odd_length_is_not_searched():
+    a = Arena(Arena.bytes_for(6), device="cpu")
+    a.take((3,), torch.float16, "odd")
+    assert a.check()
+
+
 def test_module_is_a_plain_helper():
     assert not hasattr(guarded, "pytest_configure") and not any(n.startswith("pytest_") for n in dir(guarded))
