@@ -1040,8 +1040,8 @@ SSAD_API int ssad_group_spatial_softmax_grad(const float* y, const float* dy, fl
 typedef struct ssad_softmax_focal_level {
   const float* logits;     /* forward input; not read by the backward (may be NULL there) */
   const int32_t* labels;
-  float* prob;             /* forward: output 1 of the op, written for every cell; backward: input */
-  float* out;              /* forward: the scalar loss; backward: dX (N x D x H x W) */
+  float* prob;             /* forward: output 1 of the op, written for every cell; backward: input; fused: output or NULL */
+  float* out;              /* forward: the scalar loss; backward and fused: dX (N x D x H x W) */
   int N, D, H, W;
 } ssad_softmax_focal_level;
 
@@ -1068,8 +1068,22 @@ SSAD_API int ssad_softmax_focal_loss_backward(const ssad_softmax_focal_level* le
                                               const float* fg_num, const float* dloss, int dloss_stride,
                                               const ssad_focal_params* params_host, ssad_stream_t stream);
 
+/* The loss and its gradient of a training step in ONE pass over the logits (one launch for all levels + the
+ * fixed-order finalize launch): a level's `out` is dX here, exactly the backward's result for
+ * prob = softmax(logits) and the HOST scalar dloss (1.0 inside a step, utils/blob.py:166-172), 0 for cells with
+ * label < 0; losses[l] is level l's loss, exactly the forward's.  A level's `prob` may be NULL: the probabilities
+ * are then kept in registers and never written; a non-null `prob` receives the forward's bits.  Logits are read
+ * once, dX is written once.  Rejections as the forward, except that a null `prob` is accepted; a null `losses` is
+ * SSAD_E_BADARG.  The workspace is the forward's (ssad_softmax_focal_loss_fused_workspace_bytes(n_levels) always
+ * suffices; the launcher asks for 8 bytes per workgroup it starts). */
+SSAD_API size_t ssad_softmax_focal_loss_fused_workspace_bytes(int n_levels);
+SSAD_API int ssad_softmax_focal_loss_fused(const ssad_softmax_focal_level* levels_host, int n_levels,
+                                           const float* fg_num, float dloss, const ssad_focal_params* params_host,
+                                           float* losses, void* workspace, size_t workspace_bytes,
+                                           ssad_stream_t stream);
+
 /* ---------------------------------------------------------------------- */
-/* Introspection                                                           */
+/* Introspection                                                          */
 /* ---------------------------------------------------------------------- */
 SSAD_API const char* ssad_kernels_arch(void);   /* "gfx950" */
 /* ABI version of this header.  History: 2 -> 3 (round 4): ssad_sgd_segment grew row_len / row_scale

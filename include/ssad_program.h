@@ -190,7 +190,10 @@ enum ssad_opcode {
   /* ssad_split_absmax(p0 = x, l0 = elements, p1 = word) */
   SSAD_OP_SPLIT_ABSMAX = 81,
   /* ssad_gemm_split_pack_filters(p0 = const ssad_gemm_pack_entry* (host), i0 = entries) */
-  SSAD_OP_GEMM_SPLIT_PACK = 82
+  SSAD_OP_GEMM_SPLIT_PACK = 82,
+  /* ssad_softmax_focal_loss_fused(p0 = levels_host, i0 = n, p1 = fg_num, f0 = dloss, p2 = params_host, p3 = losses,
+   * p4 = workspace, l0 = workspace_bytes) */
+  SSAD_OP_SOFTMAX_FOCAL_FUSED = 83
 };
 
 typedef struct ssad_op {

@@ -26,6 +26,9 @@
 // do not depend on timing.  A level's workgroup count depends on that level's shape alone, so a
 // five-level call and five one-level calls produce the same bits.
 //
+// A training step needs neither P nor a device-side dloss: softmax_focal_fused_kernel is the forward and the
+// backward kernel joined at the cell's registers (logits read once, dX written once, the same reduction).
+//
 // All offsets are 64-bit: N*A*C*H*W may exceed 2^31.
 
 #include <hip/hip_runtime.h>
@@ -60,8 +63,8 @@ struct Geometry {
 struct Level {
   const float* x;        // logits (forward) -- unused by the gradient
   const int32_t* g;      // labels, one per cell
-  float* p;              // probabilities: written by the forward, read by the gradient
-  float* out;            // forward: the scalar loss; gradient: dX
+  float* p;              // probabilities: written by the forward, read by the gradient; fused: written, or null
+  float* out;            // forward: the scalar loss; gradient and fused: dX (finalize: the scalar loss)
   Geometry geo;
   int block_start;       // first blockIdx.x of this level
   int blocks;            // workgroups of this level
@@ -307,6 +310,60 @@ __global__ __launch_bounds__(kThreads) void softmax_focal_bwd_kernel(
   }
 }
 
+// Loss and dX of a training step in ONE pass over the logits (the forward and the backward kernel above, joined at
+// the cell's registers): inside a step dloss is a constant and nobody reads P, so the logits are read once, dX is
+// written once, and P goes to memory only for a level that has a P pointer.  Same formulas, same order of the
+// operations as the pair; L.out is dX here and the level's loss is written by the finalize launch.  An ignored
+// cell is computed like any other (straight-line code: its label matches no class) and selected away at the store,
+// so a NaN in its logits reaches neither dX nor the loss.
+template <bool FAST, int CMAX>
+__global__ __launch_bounds__(kThreads) void softmax_focal_fused_kernel(
+    const Args args, const float* __restrict__ fg_num, const float dl, double* __restrict__ partials) {
+  const Level& L = args.lv[find_level(args, blockIdx.x)];
+  const int lb = blockIdx.x - L.block_start;
+  const int C = args.C;
+  const unsigned hw = L.geo.hw;
+  const float np = fmaxf(fg_num[0], 1.0f);
+  const float z_bg = (1.0f - args.alpha) / np, z_fg = args.alpha / np;
+  const float gamma = args.gamma, scale = args.scale;
+  const bool want_p = L.p != nullptr;           // wave-uniform
+  double acc = 0.0;
+  for (long long item = lb; item < L.geo.items; item += L.blocks) {
+    long long slab;
+    unsigned pos;
+    if (!locate(L.geo, item, &slab, &pos)) continue;
+    const size_t off = (size_t)slab * C * hw;
+    const int label = (L.g + (size_t)slab * hw)[pos];
+    float v[CMAX];
+    load_cell<CMAX, true>(L.x + off, hw, pos, C, -FLT_MAX, v);
+    softmax_cell<FAST, CMAX>(v);
+    float pl = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) pl = (c == label) ? v[c] : pl;
+    if (want_p) {
+      float* __restrict__ po = L.p + off;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c) if (c < C) (po + (size_t)c * hw)[pos] = v[c];
+    }
+    const bool live = label >= 0;
+    float pg, pgm1;
+    pow_pair(1.0f - pl, gamma, pg, pgm1);
+    const float z = label == 0 ? z_bg : z_fg;
+    const float lg = log_f<FAST>(fmaxf(pl, FLT_MIN));
+    if (live) acc += (double)(-(pg * lg) * z);
+    const float w = (-pg + gamma * pgm1 * pl * lg) * z;
+    const float k = dl * w;
+    float* __restrict__ o = L.out + off;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      const float d = (k * ((c == label ? 1.0f : 0.0f) - v[c])) * scale;
+      if (c < C) (o + (size_t)c * hw)[pos] = live ? d : 0.0f;
+    }
+  }
+  const double t = block_sum(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
 // ---- host side ---------------------------------------------------------------
 
 bool accurate_math() {
@@ -351,7 +408,7 @@ int grid_for(long long items, int cap) { return (int)(items < cap ? items : cap)
 // Level table of the focal loss: validates, assigns each level min(items, kLevelBlocks) workgroups (a
 // function of that level alone).
 int build_args(const ssad_softmax_focal_level* lv, int n_levels, const ssad_focal_params* P, bool backward,
-               Args* out, int* total_blocks) {
+               Args* out, int* total_blocks, bool fused = false) {
   if (!lv || !P || n_levels < 0 || n_levels > SSAD_MAX_LEVELS) return SSAD_E_BADARG;
   if (!classes_ok(P->num_classes) || !(P->scale >= 0.0f)) return SSAD_E_BADARG;
   Args& a = *out;
@@ -361,7 +418,8 @@ int build_args(const ssad_softmax_focal_level* lv, int n_levels, const ssad_foca
   int start = 0;
   for (int l = 0; l < n_levels; ++l) {
     const ssad_softmax_focal_level& s = lv[l];
-    if (!s.labels || !s.prob || !s.out || (!backward && !s.logits)) return SSAD_E_BADARG;
+    // (the fused pass writes P only where a level has a P pointer)
+    if (!s.labels || (!s.prob && !fused) || !s.out || (!backward && !s.logits)) return SSAD_E_BADARG;
     if (s.D <= 0 || s.D % P->num_classes != 0) return SSAD_E_BADARG;
     Level& L = a.lv[l];
     if (!geometry(s.N, s.D / P->num_classes, s.H, s.W, &L.geo)) return SSAD_E_BADARG;
@@ -439,6 +497,30 @@ int ssad_softmax_focal_loss_backward(const ssad_softmax_focal_level* levels_host
   if (n_levels == 0) return 0;
   LAUNCH_BY_CLASSES(softmax_focal_bwd_kernel, a.C, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, a, fg_num,
                     dloss, dloss_stride);
+  return (int)hipGetLastError();
+}
+
+size_t ssad_softmax_focal_loss_fused_workspace_bytes(int n_levels) {
+  return ssad_softmax_focal_loss_workspace_bytes(n_levels);
+}
+
+int ssad_softmax_focal_loss_fused(const ssad_softmax_focal_level* levels_host, int n_levels, const float* fg_num,
+                                  float dloss, const ssad_focal_params* params_host, float* losses, void* workspace,
+                                  size_t workspace_bytes, ssad_stream_t stream) {
+  Args a;
+  int blocks = 0;
+  const int rc = build_args(levels_host, n_levels, params_host, false, &a, &blocks, true);
+  if (rc) return rc;
+  if (!fg_num || !losses) return SSAD_E_BADARG;
+  if (n_levels == 0) return 0;
+  if (!workspace || workspace_bytes < sizeof(double) * (size_t)blocks) return SSAD_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  double* partials = (double*)workspace;
+  LAUNCH_BY_CLASSES(softmax_focal_fused_kernel, a.C, dim3(blocks), dim3(kThreads), 0, s, a, fg_num, dloss, partials);
+  Args fin = a;                  // the finalize launch writes out[0]: level l's loss is losses[l]
+  for (int l = 0; l < n_levels; ++l) fin.lv[l].out = losses + l;
+  hipLaunchKernelGGL(softmax_focal_finalize_kernel, dim3(n_levels), dim3(kThreads), 0, s, fin,
+                     (const double*)partials);
   return (int)hipGetLastError();
 }
 

@@ -129,6 +129,10 @@ int run_op(const ssad_op& o, ssad_stream_t s) {
     case SSAD_OP_FOCAL_BWD:
       return ssad_focal_loss_backward((const ssad_distill_level*)p[0], i[0], (const float*)p[1],
                                       (const float*)p[2], i[1], (const ssad_focal_params*)p[3], s);
+    case SSAD_OP_SOFTMAX_FOCAL_FUSED:
+      return ssad_softmax_focal_loss_fused((const ssad_softmax_focal_level*)p[0], i[0], (const float*)p[1], f[0],
+                                           (const ssad_focal_params*)p[2], (float*)p[3], (void*)p[4],
+                                           (size_t)o.l[0], s);
     case SSAD_OP_SMOOTH_L1:
       return ssad_select_smooth_l1_levels((const ssad_smooth_l1_level*)p[0], i[0], (const float*)p[1],
                                           (const float*)p[2], f[0], f[1], i[1], (void*)p[3],

@@ -35,7 +35,13 @@ from . import program as PR
 from . import synth
 from .data_parallel import BucketedAllReduce
 from .engines import Engine, Switches, conv_table, emit_packs, filter_floats, same_engine, subnet_engine
-from .modeling.retinanet_heads import HeadConfig
+from .modeling.retinanet_heads import HeadConfig, retinanet_bias_init
+
+
+def cls_group(cfg):
+    """Channels of cls_pred per anchor: the foreground classes of the sigmoid head, or all classes with the
+    background for the softmax head (RETINANET.SOFTMAX, retinanet_heads.py:78-80)."""
+    return cfg.num_classes if cfg.softmax else cfg.num_classes - 1
 
 
 def head_param_specs(cfg):
@@ -44,7 +50,7 @@ def head_param_specs(cfg):
     cls and bbox subnet interleaved (their layers of equal depth run in the
     same launches).  Bucket "late" (ready first) = predictions + upper half of
     the towers, bucket "early" = lower half."""
-    A, C, D = cfg.num_anchors, cfg.num_classes - 1, cfg.fpn_dim
+    A, C, D = cfg.num_anchors, cls_group(cfg), cfg.fpn_dim
     specs = []
 
     def add(stem, cout, bucket):
@@ -91,7 +97,10 @@ class DistillHeads(object):
     """One training iteration of the RetinaNet subnets as a native program
     (program.Program -> ssad_program_run).  distill=False is plain RetinaNet training
     (BASELINE config 2: model_builder.py:98-100,413 without the distillation wrapper): no
-    teacher, no PowSum / SigmoidAdaptiveDistillLoss, only SigmoidFocalLoss + SelectSmoothL1Loss."""
+    teacher, no PowSum / SigmoidAdaptiveDistillLoss, only SigmoidFocalLoss + SelectSmoothL1Loss.
+    HeadConfig.softmax (RETINANET.SOFTMAX, distill=False only): cls_pred has A * num_classes rows, initialised with
+    the builder's prior bias, and the loss segment is ONE SOFTMAX_FOCAL_FUSED record (SoftmaxFocalLoss and its
+    gradient in one pass over the logits) + SelectSmoothL1Loss; DESIGN 3.11a."""
 
     F16 = False
 
@@ -106,6 +115,14 @@ class DistillHeads(object):
         self.cfg = cfg or HeadConfig()
         self.N, self.shapes, self.device = N, list(shapes), device
         self.distill = bool(distill)
+        if self.cfg.softmax and self.distill:
+            raise K.KernelError(
+                "DistillHeads: HeadConfig.softmax with distill=True is not supported: SigmoidAdaptiveDistillLoss does "
+                "not take a softmax head (HeadConfig.softmax); the reference's distillation loss is sigmoid-shaped "
+                "too.  Build the softmax head with distill=False")
+        if self.cfg.softmax and self.F16:
+            raise K.KernelError("DistillHeadsF16: HeadConfig.softmax is not supported (there is no fp16 softmax "
+                                "head; the fp32 pipeline DistillHeads runs it)")
         self.teacher_bbox_tower = teacher_bbox_tower and self.distill
         self.switches = Switches.read().for_subnets(self.distill, self.F16)     # the one read of the engine switches
         self.split_conv = self.switches.split_conv
@@ -114,13 +131,18 @@ class DistillHeads(object):
         self.pg, self.world_size = process_group, world_size
         self.dp = BucketedAllReduce(process_group, world_size)
         cfg = self.cfg
-        self.A, self.C, self.D = cfg.num_anchors, cfg.num_classes - 1, cfg.fpn_dim
+        # C: cls_pred channels per anchor (softmax head: the background included)
+        self.A, self.C, self.D = cfg.num_anchors, cls_group(cfg), cfg.fpn_dim
         self.Dt = int(teacher_fpn_dim) if (teacher_fpn_dim and self.distill) else self.D
         if self.Dt != self.D and self.F16:
             raise K.KernelError("DistillHeadsF16: teacher_fpn_dim %d != fpn_dim %d is not supported (the fp16 subnets "
                                 "run teacher and student towers as one launch of one width)" % (self.Dt, self.D))
         t_cfg = cfg if self.Dt == self.D else dataclasses.replace(cfg, fpn_dim=self.Dt)
         self._plan_engines(cfg, t_cfg if self.distill else None)
+        if cfg.softmax and student_init is None:
+            # the builder's GivenTensorFill prior: the background channel of every anchor (retinanet_heads.py:39-52)
+            student_init = {"retnet_cls_pred_fpn%d_b" % cfg.k_min:
+                            np.asarray(retinanet_bias_init(cfg)[1]["values"], np.float32).reshape(-1)}
         self.params = FlatParams(cfg, device, student_init)
         self.teacher = FlatParams(t_cfg, device, teacher_init) if self.distill else None
         self.grads = FlatParams(cfg, device)
@@ -484,6 +506,21 @@ class DistillHeads(object):
             arr_b = self._cls_table(self.d_cls_logits)
             P.add(PR.DISTILL_BWD, 13, i=(nlev, 1), p=(arr_b, self.normalizer, self.one, DP),
                   work=12.0 * n_logits + 4.0 * n_labels)
+        elif cfg.softmax:
+            # SoftmaxFocalLoss and its gradient in one pass over the logits: the probabilities stay in registers
+            # (no P pointer), the loss gradient 1.0 is folded in on the host
+            arr = (K.SoftmaxFocalLevel * nlev)()
+            for l, x in enumerate(self.cls_logits):
+                N, Dd, H, W = x.shape
+                arr[l] = K.SoftmaxFocalLevel(x.data_ptr(), self.labels[l].data_ptr(), 0,
+                                             self.d_cls_logits[l].data_ptr(), N, Dd, H, W)
+            self._label_tables.append(arr)
+            SP = K.FocalParams(cfg.focal_gamma, cfg.focal_alpha, cfg.num_classes, cfg.loss_scale)
+            nb = L.ssad_softmax_focal_loss_fused_workspace_bytes(nlev)
+            ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            P.add(PR.SOFTMAX_FOCAL_FUSED, 17, i=(nlev,), f=(1.0,), l=(nb,),
+                  p=(arr, self.fg_num, SP, self.focal_losses, ws),
+                  work=8.0 * n_logits + 4.0 * n_labels, keep=list(self.cls_logits) + list(self.d_cls_logits))
         else:
             nb = L.ssad_distill_loss_workspace_bytes(nlev)
             ws = torch.empty(nb, dtype=torch.uint8, device=self.device)

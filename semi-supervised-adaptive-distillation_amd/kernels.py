@@ -164,6 +164,10 @@ def lib():
         C.POINTER(SoftmaxFocalLevel), i32, vp, C.POINTER(FocalParams), vp, sz, vp]
     L.ssad_softmax_focal_loss_backward.argtypes = [
         C.POINTER(SoftmaxFocalLevel), i32, vp, vp, i32, C.POINTER(FocalParams), vp]
+    L.ssad_softmax_focal_loss_fused_workspace_bytes.restype = sz
+    L.ssad_softmax_focal_loss_fused_workspace_bytes.argtypes = [i32]
+    L.ssad_softmax_focal_loss_fused.argtypes = [
+        C.POINTER(SoftmaxFocalLevel), i32, vp, C.c_float, C.POINTER(FocalParams), vp, vp, sz, vp]
     L.ssad_select_smooth_l1_workspace_bytes.restype = sz
     L.ssad_select_smooth_l1_workspace_bytes.argtypes = [i32]
     L.ssad_select_smooth_l1_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32,
@@ -531,6 +535,45 @@ def softmax_focal_loss_backward(levels, probs, fg_num, dloss, *, gamma=1.0, alph
     _check(L.ssad_softmax_focal_loss_backward(arr, n, _ptr(fg_num), _ptr(dloss), stride, C.byref(P), _stream()),
            "softmax_focal_loss_backward")
     return outs
+
+
+def softmax_focal_loss_fused(levels, fg_num, *, num_classes=81, gamma=1.0, alpha=0.25, scale=1.0, dloss=1.0,
+                             probs=None, out=None, workspace=None):
+    """SoftmaxFocalLoss and its gradient in one pass over the logits (what a training step needs: dloss is a host
+    constant and the probabilities stay in registers).  levels as softmax_focal_loss_forward's; probs: None, or a
+    list with a tensor (written as the forward writes it) or None per level; out: (losses [n_levels], list of dX);
+    workspace: a uint8 device tensor of at least 8 bytes per workgroup of the call
+    (ssad_softmax_focal_loss_fused_workspace_bytes(n) always suffices).  Returns (losses, list of dX)."""
+    L = lib()
+    n = len(levels)
+    losses, outs = out if out is not None else (None, None)
+    if losses is None:
+        losses = torch.empty(n, dtype=torch.float32, device="cuda")
+    if outs is None:
+        outs = [torch.empty_like(x) for x, _ in levels]
+    if probs is None:
+        probs = [None] * n
+    if _f32c(losses, "losses").numel() < n or len(outs) != n or len(probs) != n:
+        raise KernelError("softmax_focal_loss_fused: %d levels need %d losses, dX tensors and probs entries" % (n, n))
+    for (x, _), o in zip(levels, outs):
+        if _f32c(o, "out").shape != _f32c(x, "logits").shape:
+            raise KernelError("out must have the logits' shape")
+    # (the sibling's checks of logits, labels and P; a level without P borrows its logits for them)
+    arr = _softmax_focal_levels(levels, [p if p is not None else x for p, (x, _) in zip(probs, levels)], outs, True)
+    for i, p in enumerate(probs):
+        if p is None:
+            arr[i].prob = None
+    P = FocalParams(gamma, alpha, num_classes, scale)
+    nb = L.ssad_softmax_focal_loss_fused_workspace_bytes(n)
+    if workspace is None:
+        workspace = _workspace(nb, "softmaxfocal")
+    else:
+        if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or not workspace.is_cuda:
+            raise KernelError("workspace must be a contiguous uint8 device tensor")
+        nb = workspace.numel()
+    _check(L.ssad_softmax_focal_loss_fused(arr, n, _ptr(fg_num), float(dloss), C.byref(P), _ptr(losses),
+                                           _ptr(workspace), nb, _stream()), "softmax_focal_loss_fused")
+    return losses, outs
 
 
 def cls_losses_fused(levels, normalizer, fg_num, distill_kw, focal_kw, out=None, losses=None):

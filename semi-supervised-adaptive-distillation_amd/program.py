@@ -29,6 +29,7 @@ PW_F16, PW_F16_PACK, PW_F16_WGRAD, F16_EW, STEM_POOL_F16, GROUPED_F16, GROUPED_F
 CONV_IMPLICIT_WS, CONV_KXK_WGRAD, CONV_KXK_DGRAD, TRANSPOSE_FILTERS, F16_PACK_FILTERS = 74, 75, 76, 77, 78
 GEMM_CONV_SPLIT = 79
 SPLIT_ABSMAX_LEVELS, SPLIT_ABSMAX, GEMM_SPLIT_PACK = 80, 81, 82
+SOFTMAX_FOCAL_FUSED = 83
 
 # timing classes: one per kernel family.  bound "mfma": work = direct-form FLOPs
 # (2*9*Cout*Cin per output pixel; the Winograd engine executes 1/2.25 of them);
@@ -53,6 +54,7 @@ KLASS = {
     13: dict(name="SigmoidAdaptiveDistillLoss bwd (distill_bwd_kernel)", bound="hbm"),
     14: dict(name="SigmoidFocalLoss fwd (focal_fwd_kernel + finalize)", bound="hbm"),
     15: dict(name="SigmoidFocalLoss bwd (focal_bwd_kernel)", bound="hbm"),
+    17: dict(name="SoftmaxFocalLoss fwd+bwd in one pass (softmax_focal_fused_kernel + finalize)", bound="hbm"),
     # the frozen teacher on the Winograd F(2x4, 3x3) engine: executed multiplies = direct-form / 3
     20: dict(name="teacher cls_pred conv3x3 fwd + sigmoid, 720-wide, F(2x4,3x3) (wino24_conv_kernel)", bound="mfma",
              wino=True, exec_div=3.0),

@@ -80,8 +80,9 @@ def initialize_from_weights_file(store, weights_file, teacher_weights_file=None,
     are then fed too.  Returns the lists of loaded and missing parameter names.
 
     softmax: the head is the RETINANET.SOFTMAX one -- `retnet_cls_pred_fpn<k_min>_w/_b` carry
-    A * num_classes output channels, background included (`store` is then a HeadParamStore of a
-    HeadConfig(softmax=True), or anything whose cls_pred parameters have that shape).  Without it a
+    A * num_classes output channels, background included (`store` is then a HeadParamStore or a
+    DistillHeads(distill=False) of a HeadConfig(softmax=True), or anything whose cls_pred parameters have that shape;
+    a whole NativeDistillModel says it itself, through its heads' configuration).  Without it a
     softmax-shaped cls_pred blob is what it is to a sigmoid head: another shape, reported and skipped
     -- also when the store itself is softmax-shaped, so a sigmoid pipeline is never fed by accident."""
     logger.info("Loading weights from: %s", weights_file)
@@ -126,7 +127,8 @@ def _initialize_heads(store, src, teacher_file_given=False, softmax=False):
         loaded.append(name)
         if mname in src:
             _feed(store.moms, name, src[mname])
-    for name, _, _, _ in store.teacher.specs:
+    # (no teacher: DistillHeads(distill=False), the only native pipeline a softmax head runs in)
+    for name, _, _, _ in store.teacher.specs if store.teacher is not None else ():
         tname = "teacher/" + name
         if tname not in src:
             if teacher_file_given or any(k.startswith("teacher/") for k in src):
@@ -453,7 +455,9 @@ def native_model_from_weights_files(heads, weights_file, teacher_weights_file=No
 def initialize_from_blobs(model, src, strict=False):
     """Feed a built NativeDistillModel (subnets + both backbones) from a blob dict that already
     carries the teacher under `teacher/`.  strict: see load_backbone."""
-    loaded, missing = _initialize_heads(model.heads, src)
+    # (a model built with softmax heads says so itself: its cls_pred takes the softmax-shaped blob, and a
+    # sigmoid-shaped one is reported and skipped like any other mis-shaped blob)
+    loaded, missing = _initialize_heads(model.heads, src, softmax=_softmax_store(model.heads))
     nets = [(model.student, "")] + ([(model.teacher, "teacher/")] if model.teacher is not None else [])
     for net, prefix in nets:
         load_backbone(net, src, prefix, load_momentum=not prefix, strict=strict)
