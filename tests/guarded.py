@@ -9,8 +9,13 @@ output and workspace of a launch.  After the launch `check()` asserts that
     after the last) still holds the sentinel;
   * every view that was taken with `data` and is not named in `modified` is bit-identical to its host copy
     (operands are frozen);
-  * no output (a view taken without `data`, of 4-byte elements or of 2-byte elements, a byte length that is a multiple
-    of 4 and a 4-byte-aligned start) still holds a sentinel word, except where the caller says the reference has a NaN.
+  * no output (a view taken without `data`, of 4-byte or 8-byte elements, or of 2-byte elements, a byte length that
+    is a multiple of 4 and a 4-byte-aligned start) still holds a sentinel word, except where the caller says the
+    reference has a NaN.  An 8-byte element (float64, int64) counts as unwritten when BOTH of its 32-bit halves hold
+    the sentinel word; 1-byte outputs are not searched (their tests assert the value set themselves).
+
+`untouched(name)` is the query for outputs whose contract is "rows past the count are not written": `nan_ok` excuses
+those rows in `check()`, and the test then asserts, word for word, that they still hold the sentinel.
 
 An overrun longer than a guard lands in a neighbouring view; that is still caught, by the frozen-operand check or by
 the test's comparison with its oracle.
@@ -110,6 +115,23 @@ class Arena:
 
     # ---- checking ----------------------------------------------------------------------------------------------
 
+    def untouched(self, name):
+        """Boolean numpy mask, one flag per 4-byte word of the view `name`, true where the word still holds the
+        sentinel: the view's shape for 4-byte elements, shape + (2,) for 8-byte elements, flat otherwise (the byte
+        length must then be a multiple of 4).  Synchronises first."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        v = next((v for v in self.views if v.name == name), None)
+        assert v is not None, "untouched(): no view named %r" % name
+        assert v.nbytes % 4 == 0 and v.off % 4 == 0, "untouched(): view %r is not made of whole words" % name
+        left = (self.bytes[v.off:v.off + v.nbytes].view(torch.int32) == SENTINEL).cpu().numpy()
+        item = v.tensor.element_size()
+        if item == 4:
+            return left.reshape(tuple(v.tensor.shape))
+        if item == 8:
+            return left.reshape(tuple(v.tensor.shape) + (2,))
+        return left
+
     def _nearest(self, a):
         """(view, offset relative to it as text) of absolute arena offset a"""
         best, dist = None, None
@@ -154,13 +176,18 @@ class Arena:
                                          % (v.name, len(np.unique(diff // 4)), int(diff[0])))
         for v in self.views:
             item = v.tensor.element_size()
-            if v.kind != "output" or not (item == 4 or (item == 2 and v.nbytes % 4 == 0 and v.off % 4 == 0)):
+            if v.kind != "output" or not (item in (4, 8) or (item == 2 and v.nbytes % 4 == 0 and v.off % 4 == 0)):
                 continue
             ok = (nan_ok or {}).get(v.name)
             if ok is True:
                 continue
             if item == 4:
                 left = (v.tensor.view(torch.int32) == SENTINEL).cpu().numpy()
+                if ok is not None:
+                    left &= ~np.asarray(ok, bool).reshape(left.shape)
+            elif item == 8:                        # unwritten only if both halves hold the sentinel word
+                left = (v.tensor.reshape(-1).view(torch.int32) == SENTINEL).cpu().numpy()
+                left = left.reshape(tuple(v.tensor.shape) + (2,)).all(axis=-1)
                 if ok is not None:
                     left &= ~np.asarray(ok, bool).reshape(left.shape)
             else:                                  # words of two halves, in memory order
@@ -171,6 +198,6 @@ class Arena:
                 first = int(np.flatnonzero(left)[0])
                 raise AssertionError("output %r not written completely: %d word(s) still hold the sentinel, the first at "
                                      "byte %d of the view (element %s)"
-                                     % (v.name, int(left.sum()), 4 * first,
+                                     % (v.name, int(left.sum()), (8 if item == 8 else 4) * first,
                                         tuple(int(i) for i in np.unravel_index(first, left.shape))))
         return True

@@ -13,6 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SCORING = ("ID", "TEMP_AVG", "AVG", "IOU_AVG", "GENERALIZED_AVG", "QUASI_SUM")      # the fixture's numbering
 METHODS = {0: "hard", 1: "linear", 2: "gaussian"}                                   # the reference's numbering
 SHAPES = [(20, 28), (10, 14), (5, 7)]
+GAUSS_TOL = 1e-4       # relative: decayed gaussian scores (expf), and what the detector builds from them
+VOTE_TOL = 1e-4        # voted boxes (relative + of the largest coordinate) and voted scores (relative)
 
 
 @pytest.fixture(scope="module")
@@ -63,7 +65,7 @@ def test_gaussian_same_picks_and_scores_within_parity_tolerance(B, z):
         assert np.array_equal(keep, z["soft_keep_%d" % v]), v
         worst = max(worst, float(np.max(np.abs(out[:, 4].astype(np.float64) - want) / want)))
     print("gaussian soft-NMS: max relative score error %.3e over %d cases" % (worst, len(cases)))
-    assert worst <= 1e-4, "max relative error of the decayed scores %.3e" % worst
+    assert worst <= GAUSS_TOL, "max relative error of the decayed scores %.3e" % worst
 
 
 def raw_soft_nms(dets, cls, classes, method, sigma=0.5, nt=0.3, thresh=0.001):
@@ -134,10 +136,10 @@ def test_box_voting_matches_the_reference(B, z):
         big = float(np.abs(z["vote_all_%d" % a][:, :4]).max())
         err = np.abs(got[:, :4].astype(np.float64) - want[:, :4])
         worst_box = max(worst_box, float((err / big).max()))
-        assert np.all(err <= 1e-4 * np.abs(want[:, :4]) + 1e-4 * big), (k, float(err.max()), big)
+        assert np.all(err <= VOTE_TOL * np.abs(want[:, :4]) + VOTE_TOL * big), (k, float(err.max()), big)
         rel = np.abs(got[:, 4].astype(np.float64) - want[:, 4]) / np.abs(want[:, 4])
         worst_score = max(worst_score, float(rel.max()))
-        assert rel.max() <= 1e-4, (k, SCORING[int(z["vote_scoring"][k])], float(rel.max()))
+        assert rel.max() <= VOTE_TOL, (k, SCORING[int(z["vote_scoring"][k])], float(rel.max()))
         if SCORING[int(z["vote_scoring"][k])] == "ID":
             assert np.array_equal(got[:, 4], z["vote_top_%d" % t][:, 4])
     print("box voting: max box error %.3e of the largest coordinate, max relative score error %.3e over %d cases" % (
@@ -255,8 +257,8 @@ def test_detector_options_equal_the_per_class_composition(B, all_candidates, sof
     if exact:
         assert got.tobytes() == want.tobytes()
     else:
-        np.testing.assert_allclose(got[:, 4], want[:, 4], rtol=1e-4, atol=0)
-        np.testing.assert_allclose(got[:, :4], want[:, :4], rtol=1e-4, atol=1e-4 * 210)
+        np.testing.assert_allclose(got[:, 4], want[:, 4], rtol=GAUSS_TOL, atol=0)
+        np.testing.assert_allclose(got[:, :4], want[:, :4], rtol=GAUSS_TOL, atol=GAUSS_TOL * 210)
     again = det(probs, deltas, 150, 210, 1.0).cpu().numpy()
     assert again.tobytes() == got.tobytes()
 

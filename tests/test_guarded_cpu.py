@@ -174,5 +174,73 @@ def test_fp16_output_of_odd_length_is_not_searched():
     assert a.check()
 
 
+def fresh64():
+    rng = np.random.default_rng(2)
+    a = Arena(Arena.bytes_for(8 * 6, 8 * 6, 8 * 3, 5), device="cpu")
+    x = a.take((2, 3), torch.float64, "x", data=rng.standard_normal((2, 3)))
+    y = a.take((2, 3), torch.float64, "y")
+    k = a.take((3,), torch.int64, "k")
+    return a, x, y, k
+
+
+def test_half_written_float64_output_is_reported():
+    """an 8-byte element is unwritten when BOTH halves hold the sentinel word; a fully written view passes"""
+    a, x, y, k = fresh64()
+    y.copy_(x)
+    k.fill_(-1)
+    assert a.check()                                               # fully written: passes
+    a, x, y, k = fresh64()
+    y[0].copy_(x[0])
+    k.fill_(0)
+    with pytest.raises(AssertionError, match=r"output 'y' not written completely: 3 word\(s\).*byte 24 of the view "
+                                             r"\(element \(1, 0\)\)"):
+        a.check()
+    ok = np.zeros((2, 3), bool)
+    ok[1] = True
+    assert a.check(nan_ok={"y": ok})
+    ok[1, 2] = False
+    with pytest.raises(AssertionError, match=r"output 'y' not written completely: 1 word"):
+        a.check(nan_ok={"y": ok})
+    # one written half is a written element: 2^32 * k + sentinel in the low half is a value an int64 may hold
+    a, x, y, k = fresh64()
+    y.copy_(x)
+    k.fill_(0)
+    k.view(torch.int32)[2] = SENTINEL
+    y.reshape(-1).view(torch.int32)[5] = SENTINEL
+    assert a.check()
+    k.view(torch.int32)[3] = SENTINEL
+    with pytest.raises(AssertionError, match=r"output 'k' not written completely: 1 word\(s\).*byte 8 "):
+        a.check()
+
+
+def test_one_byte_outputs_are_not_searched():
+    a = Arena(Arena.bytes_for(8), device="cpu")
+    a.take((8,), torch.uint8, "flags")
+    assert a.check()                                               # their tests assert the value set themselves
+    assert a.untouched("flags").shape == (2,) and a.untouched("flags").all()
+
+
+def test_untouched_sees_a_one_word_write():
+    a, x, y, ws, word = fresh()
+    u = a.untouched("y")
+    assert u.shape == (5, 7) and u.dtype == bool and u.all()
+    y[3, 4] = 0.0
+    u = a.untouched("y")
+    assert not u[3, 4] and u.sum() == 34
+    y.view(torch.int32)[3, 4] = SENTINEL                           # the sentinel's own bits count as untouched
+    assert a.untouched("y").all()
+    assert not a.untouched("x").any()                              # an input: nothing of it is sentinel
+    a, x, y, k = fresh64()
+    u = a.untouched("y")
+    assert u.shape == (2, 3, 2) and u.all()
+    y.reshape(-1).view(torch.int32)[3] = 0                         # the high half of element (0, 1)
+    u = a.untouched("y")
+    assert not u[0, 1, 1] and u[0, 1, 0] and u.sum() == 11
+    a, x, y = fresh16()
+    assert a.untouched("y").shape == (24,)                         # 2-byte elements: flat words
+    with pytest.raises(AssertionError, match="no view named"):
+        a.untouched("nope")
+
+
 def test_module_is_a_plain_helper():
     assert not hasattr(guarded, "pytest_configure") and not any(n.startswith("pytest_") for n in dir(guarded))
