@@ -99,36 +99,22 @@ class NativeResNetFPNF16(NativeResNetFPN):
         arr[0].x, arr[0].dy = x.data_ptr(), dy.data_ptr()
         arr[0].N, arr[0].H, arr[0].W = x.shape[0], x.shape[2], x.shape[3]
         nb = K.lib().ssad_conv3x3_wgrad_f16_levels_workspace_bytes(arr, 1, layer.cin, layer.cout)
-        self._ws_need = max(self._ws_need, nb)
-        self._aux(P)
-        idx = P.add(PR.F16_WGRAD, KL_W3, i=(1, layer.cin, layer.cout, 0), f=(1.0,), l=(nb,),
-                    p=(arr, self.inv_scale, layer.gw, layer.gb, None),
-                    work=2.0 * 9 * layer.cout * layer.cin * x.shape[0] * x.shape[2] * x.shape[3], keep=[x, dy],
-                    stream=self._wstream)
-        self._ws_ops.append((idx, 4, self._wstream))
+        stream, ws = self._aux(P)
+        P.add(PR.F16_WGRAD, KL_W3, i=(1, layer.cin, layer.cout, 0), f=(1.0,), l=(nb,),
+              p=(arr, self.inv_scale, layer.gw, layer.gb, ws.need(nb)),
+              work=2.0 * 9 * layer.cout * layer.cin * x.shape[0] * x.shape[2] * x.shape[3], keep=[x, dy], stream=stream)
 
     def _wg1(self, P, x, dy, layer):
         N, H, W = x.shape[0], x.shape[2], x.shape[3]
         nb = K.lib().ssad_conv1x1_wgrad_f16_workspace_bytes(N, layer.cin, H, W, layer.cout)
-        self._ws_need = max(self._ws_need, nb)
-        self._aux(P)
-        idx = P.add(PR.PW_F16_WGRAD, KL_W1, i=(N, layer.cin, H, W, layer.cout, 0), f=(1.0,), l=(nb,),
-                    p=(x, dy, self.inv_scale, layer.gw, layer.gb, None),
-                    work=2.0 * N * H * W * layer.cin * layer.cout, keep=[x, dy], stream=self._wstream)
-        self._ws_ops.append((idx, 5, self._wstream))
+        stream, ws = self._aux(P)
+        P.add(PR.PW_F16_WGRAD, KL_W1, i=(N, layer.cin, H, W, layer.cout, 0), f=(1.0,), l=(nb,),
+              p=(x, dy, self.inv_scale, layer.gw, layer.gb, ws.need(nb)),
+              work=2.0 * N * H * W * layer.cin * layer.cout, keep=[x, dy], stream=stream)
 
     # -- program construction --------------------------------------------------------------------
     def _build(self):
-        import os
-        self._ws_need, self._ws_ops = 0, []
-        ov = self._overlap_wgrad
-        on = os.environ.get("SSAD_OVERLAP_WGRAD", "1") == "1" if ov is None else ov
-        # filter / bias gradients go round-robin over this many auxiliary streams (each with its own
-        # workspace): the small reduce launch that ends one filter gradient then runs beside the next
-        # one's main kernel instead of in front of it
-        nws = 2      # 1 was indistinguishable, 3 worse
-        self._wstreams = list(range(1, nws + 1)) if on else [0]
-        self._wstream, self._wnext = self._wstreams[0], 0
+        self._aux_streams()
         L, dev, lib = self._layers, self.device, K.lib()
         inv = self._io.get("inv_scale")
         self.inv_scale = inv if inv is not None else torch.ones(1, dtype=torch.float32, device=dev)
@@ -175,19 +161,9 @@ class NativeResNetFPNF16(NativeResNetFPN):
         if self.train:
             self._emit_backward(P)
             P.mark("sgd")
-            tab = (K.SgdSegment * len(self.segments))()
-            for i, (off, n, isb, row_len, s2) in enumerate(self.segments):
-                tab[i] = K.SgdSegment(off, n, isb, row_len if s2 is not None else 0,
-                                      s2.data_ptr() if s2 is not None else None)
-            P.add(PR.SGD_FLAT, 55, i=(len(self.segments),), f=(self.momentum, self.weight_decay),
-                  p=(self.params_flat, self.grads_flat, self.moms_flat, self.lr, tab, self.skip_flag),
-                  work=4.0 * 6 * self.params_flat.numel(),
-                  keep=[s2 for (_, _, _, _, s2) in self.segments if s2 is not None])
+            self._emit_sgd(P)
         P.mark("end")
-        self.wss = {k: torch.empty(max(self._ws_need, 16), dtype=torch.uint8, device=dev) for k in self._wstreams}
-        self.ws = self.wss[self._wstreams[0]]
-        for idx, slot, k in self._ws_ops:
-            P.set_ptr(idx, slot, self.wss[k])
+        self._bind_workspaces()
         P.build()
 
     # -- forward -----------------------------------------------------------------------------------

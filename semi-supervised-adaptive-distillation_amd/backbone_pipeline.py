@@ -42,7 +42,8 @@ import torch
 from . import kernels as K
 from . import program as PR
 from .data_parallel import BucketedAllReduce
-from .engines import Engine, Switches, backbone_engine, conv_table, emit_packs, filter_floats, same_engine
+from .engines import (AmaxTable, Engine, Switches, backbone_engine, backbone_wgrad_split, emit_conv3x3,
+                      emit_conv3x3_wgrad, emit_packs, filter_floats, same_engine)
 from .modeling.resnet_fpn import ChannelRatioError, channel_widths
 
 # pixels (all images) a pointwise launch needs before the split-operand GEMM pays (see NativeResNetFPN._gemm)
@@ -344,52 +345,11 @@ class NativeResNetFPN(object):
         self._bufs.append(u)
         return u
 
-    # -- |max| words of the split-operand engines ------------------------------------------------------------
-    # One table of words per network, zeroed by ONE fill at the start of the forward pass.  A tensor is measured once,
-    # on the main stream, in front of its first split-engine consumer (SPLIT_ABSMAX / SPLIT_ABSMAX_LEVELS), and every
-    # later consumer -- the filter gradient on an auxiliary stream in particular -- is handed the word: no call measures
-    # or zeroes anything itself.  Tensors are identified by address: every activation and gradient buffer of a
-    # program is allocated once (_t / _like) and written once per step before its consumers.
+    # |max| words of the split-operand engines (engines.AmaxTable): one word per tensor.  The producers of the forward
+    # pass fold (every activation is written exactly once there) and, in the backward pass, those of the three gradients
+    # inside a bottleneck block (fold=True at their call sites); the other gradient buffers are also summed in place by
+    # element-wise kernels, which would leave a folded word stale: their first split-engine reader measures them.
     AMAX_WORDS = 4096
-
-    def _measure(self, P, tensors, channels):
-        """Slot of the first of len(tensors) consecutive |max| words of these tensors (measured together, once)."""
-        key = tuple(t.data_ptr() for t in tensors)
-        if key in self._amax_groups:
-            return self._amax_groups[key]
-        base = self._amax_next
-        self._amax_next += len(tensors)
-        if self._amax_next > self.AMAX_WORDS:
-            raise K.KernelError("|max| table full")
-        addr = self.amax.data_ptr() + 4 * base
-        if len(tensors) == 1:
-            t = tensors[0]
-            P.add(PR.SPLIT_ABSMAX, 73, p=(t, addr), l=(t.numel(),), work=4.0 * t.numel(), keep=[t])
-        else:
-            arr = conv_table([(t, None, None, None, None) for t in tensors])
-            P.add(PR.SPLIT_ABSMAX_LEVELS, 73, i=(len(tensors), channels, 0), p=(arr, addr),
-                  work=4.0 * sum(t.numel() for t in tensors), keep=list(tensors))
-        self._amax_groups[key] = base
-        for k, t in enumerate(tensors):
-            self._amax_groups[(t.data_ptr(),)] = base + k          # (the freshest measurement serves later readers)
-        return base
-
-    def _produces(self, *tensors):
-        """Slots for tensors whose PRODUCER (a split-engine kernel's epilogue) folds their |max| in: nobody has to
-        measure them.  The forward pass (every activation is written exactly once there) and, in the backward pass, the
-        three gradients inside a bottleneck block (fold=True at their call sites); the other gradient buffers are also
-        summed in place by element-wise kernels, which would leave a folded word stale."""
-        base = self._amax_next
-        self._amax_next += len(tensors)
-        if self._amax_next > self.AMAX_WORDS:
-            raise K.KernelError("|max| table full")
-        self._amax_groups[tuple(t.data_ptr() for t in tensors)] = base
-        for k, t in enumerate(tensors):
-            self._amax_groups[(t.data_ptr(),)] = base + k
-        return base
-
-    def _amax_addr(self, slot):
-        return self.amax.data_ptr() + 4 * slot
 
     def poison(self, value=float("nan")):
         """Fill every activation / gradient / scratch buffer (debugging aid: anything the step
@@ -416,12 +376,11 @@ class NativeResNetFPN(object):
         if self.switches.split_conv & 128 and Kc >= 256 and M >= 256 and px >= GEMM_SPLIT_MIN_PIXELS and klass == 50:
             nb = K.lib().ssad_conv1x1_gemm_split_workspace_bytes(C.byref(d))
             if nb:
-                self._split_need = max(self._split_need, nb)
-                xa = self._amax_addr(self._measure(P, [x], Kc))
-                ya = self._amax_addr(self._produces(y)) if (self._fwd or fold) and final and not acc else None
-                idx = P.add(PR.GEMM_CONV_SPLIT, 71, p=(d, None, self._packed_a(a, lda, Kc, M), xa, ya), l=(nb,),
-                            work=2.0 * px * Kc * M, keep=[t for t in (a, x, y, bias, res, mask) if t is not None])
-                self._gemm_split_ops.append(idx)
+                am = self._amax
+                xa = am.addr(am.measure(P, [[x]], Kc))
+                ya = am.addr(am.reserve([[y]])) if (self._fwd or fold) and final and not acc else None
+                P.add(PR.GEMM_CONV_SPLIT, 71, p=(d, self._split.need(nb), self._packed_a(a, lda, Kc, M), xa, ya),
+                      l=(nb,), work=2.0 * px * Kc * M, keep=[t for t in (a, x, y, bias, res, mask) if t is not None])
                 return
         P.add(PR.GEMM_CONV, klass, p=(d,), work=2.0 * px * Kc * M,
               keep=[t for t in (a, x, y, bias, res, mask) if t is not None])
@@ -443,41 +402,13 @@ class NativeResNetFPN(object):
 
     def _conv3(self, P, probs, Cout, Cin, flags, engine, fold=False):
         """probs: [(x, y, mask or None, packed, bias or None)]: independent 3x3 convolutions of one (Cout, Cin) in one
-        launch on one engine (the split-operand engine's workspace is bound when the program is finished)."""
-        arr = conv_table(probs)
-        px = sum(p[0].shape[0] * p[0].shape[2] * p[0].shape[3] for p in probs)
-        ptrs, sizes = (arr, None, None), ()
-        if engine == Engine.SPLIT:
-            nb = K.lib().ssad_conv3x3_split_workspace_bytes(arr, len(probs), Cin)
-            self._split_need = max(self._split_need, nb)
-            xa = self._amax_addr(self._measure(P, [p[0] for p in probs], Cin))
-            ya = self._amax_addr(self._produces(*[p[1] for p in probs])) if (self._fwd or fold) else None
-            ptrs, sizes = (arr, None, None, None, xa, ya), (nb,)
-        idx = P.add(PR.CONV3X3, self.KLASS3[self.train, engine], i=(len(probs), Cout, Cin, flags, engine), l=sizes,
-                    p=ptrs, work=2.0 * 9 * Cout * Cin * px, keep=[t for p in probs for t in p if t is not None])
-        if engine == Engine.SPLIT:
-            self._split_ops.append(idx)
+        launch on one engine."""
+        emit_conv3x3(P, self.KLASS3[self.train, engine], probs, Cout, Cin, flags, engine, self._amax, self._split,
+                     fold=self._fwd or fold)
 
     def _wgrad3(self, P, x, dy, layer):
-        arr = conv_table([(x, None, dy, None, None)])
-        # SSAD_SPLIT_CONV bit 64 (default): the >= 256-wide 3x3 filter gradients on the split-operand engine (the
-        # 128-wide res3 layers are level with the F(3x3, 2x2) engine there: 2 blocks of dW, 128 slabs to reduce)
-        split = bool(self.switches.split_conv & 64) and layer.cout >= 256 and layer.cin >= 256
-        if split and not K.lib().ssad_conv3x3_wgrad_split_workspace_bytes(arr, 1, layer.cout, layer.cin):
-            split = False           # (a tensor of 2 GiB or more: the exact engine)
-        size_fn = K.lib().ssad_conv3x3_wgrad_split_workspace_bytes if split else K.lib().ssad_conv3x3_wgrad_workspace_bytes
-        nb = size_fn(arr, 1, layer.cout, layer.cin)
-        self._ws_need = max(self._ws_need, nb)
-        xa = da = None
-        if split:            # (measured on the main stream, before the fork)
-            xa = self._amax_addr(self._measure(P, [x], layer.cin))
-            da = self._amax_addr(self._measure(P, [dy], layer.cout))
-        self._aux(P)
-        idx = P.add(PR.CONV3X3_WGRAD, 70 if split else 49, i=(1, layer.cout, layer.cin, 0, 1 if split else 0), l=(nb,),
-                    p=(arr, layer.gw, layer.gb, None, xa, da),
-                    work=2.0 * 9 * layer.cout * layer.cin * x.shape[0] * x.shape[2] * x.shape[3], keep=[x, dy],
-                    stream=self._wstream)
-        self._ws_ops.append((idx, 3, self._wstream))
+        emit_conv3x3_wgrad(P, (49, 70), [x], [dy], layer.gw, layer.gb, layer.cout, layer.cin,
+                           backbone_wgrad_split(self.switches, layer.cout, layer.cin), self._amax, self._aux)
 
     def _wgrad1(self, P, x, dy, layer):
         N, Cc = x.shape[0], x.shape[1]
@@ -490,16 +421,13 @@ class NativeResNetFPN(object):
             split = False           # (a tensor of 2 GiB or more: the exact engine)
         size_fn = K.lib().ssad_conv1x1_wgrad_split_workspace_bytes if split else K.lib().ssad_conv1x1_wgrad_workspace_bytes
         nb = size_fn(N, Cc, pix, layer.cout)
-        self._ws_need = max(self._ws_need, nb)
         xa = da = None
-        if split:
-            xa = self._amax_addr(self._measure(P, [x], Cc))
-            da = self._amax_addr(self._measure(P, [dy], layer.cout))
-        self._aux(P)
-        idx = P.add(PR.CONV1X1_WGRAD, 72 if split else 52, i=(N, Cc, pix, layer.cout, 0, 1 if split else 0), l=(nb,),
-                    p=(x, dy, layer.gw, None, xa, da), work=2.0 * N * pix * Cc * layer.cout, keep=[x, dy],
-                    stream=self._wstream)
-        self._ws_ops.append((idx, 3, self._wstream))
+        if split:            # (measured on the main stream, before the fork)
+            xa = self._amax.addr(self._amax.measure(P, [[x]], Cc))
+            da = self._amax.addr(self._amax.measure(P, [[dy]], layer.cout))
+        stream, ws = self._aux(P)
+        P.add(PR.CONV1X1_WGRAD, 72 if split else 52, i=(N, Cc, pix, layer.cout, 0, 1 if split else 0), l=(nb,),
+              p=(x, dy, layer.gw, ws.need(nb), xa, da), work=2.0 * N * pix * Cc * layer.cout, keep=[x, dy], stream=stream)
 
     def _bias_grad(self, P, dz, layer, rowsum=None):
         """db[c] = sum over n, pixels of dz; from the [N][C] plane sums when a ReluGradient pass
@@ -533,12 +461,9 @@ class NativeResNetFPN(object):
         N, Cc, H, W = x.shape
         nb = K.lib().ssad_conv_kxk_wgrad_workspace_bytes(N, Cc, H, W, layer.cout, 3, 2, 1)
         assert nb > 0
-        self._ws_need = max(self._ws_need, nb)
-        self._aux(P)
-        idx = P.add(PR.CONV_KXK_WGRAD, 65, i=(N, Cc, H, W, layer.cout, 3, 2, 1), l=(nb, 0),
-                    p=(x, dy, layer.gw, None), keep=[x, dy],
-                    work=2.0 * 9 * Cc * layer.cout * N * dy.shape[2] * dy.shape[3], stream=self._wstream)
-        self._ws_ops.append((idx, 3, self._wstream))
+        stream, ws = self._aux(P)
+        P.add(PR.CONV_KXK_WGRAD, 65, i=(N, Cc, H, W, layer.cout, 3, 2, 1), l=(nb, 0), p=(x, dy, layer.gw, ws.need(nb)),
+              keep=[x, dy], work=2.0 * 9 * Cc * layer.cout * N * dy.shape[2] * dy.shape[3], stream=stream)
         self._bias_grad(P, dy, layer)
 
     def _dgrad_s2(self, P, layer, dy, dx, mask=None):
@@ -557,18 +482,18 @@ class NativeResNetFPN(object):
         they fill the last partial round of workgroups of the chain's kernels and vice versa.  They
         share one workspace, which is safe because they are serialised on that one stream; nothing
         they read is modified by the main stream before the segment's JOIN (gradients that meet are
-        written to fresh buffers, not accumulated in place)."""
+        written to fresh buffers, not accumulated in place).  -> (the stream, its Workspace)"""
         self._wstream = self._wstreams[self._wnext % len(self._wstreams)]
         self._wnext += 1
         if self._wstream:
             P.fork(self._wstream)
+        return self._wstream, self._aux_ws[self._wstream]
 
     def _ew(self, P, code, i=(), p=(), l=(), f=(), nbytes=0.0):
         P.add(code, 51, i=i, p=p, l=l, f=f, work=nbytes)
 
     # -- program construction ----------------------------------------------------------------------
-    def _build(self):
-        self._ws_need, self._ws_ops = 0, []
+    def _aux_streams(self):
         ov = self._overlap_wgrad
         on = os.environ.get("SSAD_OVERLAP_WGRAD", "1") == "1" if ov is None else ov
         # filter / bias gradients go round-robin over this many auxiliary streams (each with its own
@@ -577,22 +502,40 @@ class NativeResNetFPN(object):
         nws = 2      # 1 was indistinguishable, 3 worse
         self._wstreams = list(range(1, nws + 1)) if on else [0]
         self._wstream, self._wnext = self._wstreams[0], 0
+        self._aux_ws = {k: PR.Workspace() for k in self._wstreams}
+        # the split-engine launches of this network run one after the other on its main stream: one workspace
+        self._split = PR.Workspace()
+
+    def _emit_sgd(self, P):
+        tab = (K.SgdSegment * len(self.segments))()
+        for i, (off, n, isb, row_len, s2) in enumerate(self.segments):
+            tab[i] = K.SgdSegment(off, n, isb, row_len if s2 is not None else 0,
+                                  s2.data_ptr() if s2 is not None else None)
+        P.add(PR.SGD_FLAT, 55, i=(len(self.segments),), f=(self.momentum, self.weight_decay),
+              p=(self.params_flat, self.grads_flat, self.moms_flat, self.lr, tab, self.skip_flag),
+              work=4.0 * 6 * self.params_flat.numel(),
+              keep=[s2 for (_, _, _, _, s2) in self.segments if s2 is not None])
+
+    def _bind_workspaces(self):
+        self.wss = {k: w.bind(self.device) for k, w in self._aux_ws.items()}
+        self.ws = self.wss[self._wstreams[0]]
+        self.split_ws = self._split.bind(self.device)
+
+    def _build(self):
+        self._aux_streams()
         # FPN's stride-2 3x3 layers (P6, P7) at their own size: implicit GEMM with split-K forward, flattened-batch
         # GEMMs for the gradients (conv_strided.hip).  SSAD_STRIDED_3X3=winograd: rounds 1-2's stride-1 Winograd
         # layer + subsampling (4x the direct-form flops), kept for A/B runs.
         self._strided_own = os.environ.get("SSAD_STRIDED_3X3", "own") != "winograd"
         self._dgrad_ws = None
         L = self._layers
-        dev = self.device
         lib = K.lib()
         # packed filters: frozen layers once (prepare program), trainable layers every step (pack segment)
         prep, P = PR.Program(), PR.Program()
         self.prep, self.prog = prep, P
         packs = {True: {}, False: {}}          # {trained?: {Engine: pack entries}}: P packs every step, prep once
-        self._split_ops, self._split_need = [], 0
-        self._gemm_split_ops = []
-        self.amax = torch.zeros(self.AMAX_WORDS, dtype=torch.int32, device=self.device)
-        self._amax_groups, self._amax_next = {}, 0
+        self._amax = AmaxTable(self.AMAX_WORDS, self.device)
+        self.amax = self._amax.tensor
         self._gemm_packs, self._gpack_train, self._gpack_frozen, self._a_train = {}, [], [], {}
         tr_frozen, tr_train = [], []          # (w, wt, M, K, ldm): every transposed filter of a program in one launch
         P.mark("pack")
@@ -649,14 +592,7 @@ class NativeResNetFPN(object):
         if self.train:
             self._emit_backward(P)
             P.mark("sgd")
-            tab = (K.SgdSegment * len(self.segments))()
-            for i, (off, n, isb, row_len, s2) in enumerate(self.segments):
-                tab[i] = K.SgdSegment(off, n, isb, row_len if s2 is not None else 0,
-                                      s2.data_ptr() if s2 is not None else None)
-            P.add(PR.SGD_FLAT, 55, i=(len(self.segments),), f=(self.momentum, self.weight_decay),
-                  p=(self.params_flat, self.grads_flat, self.moms_flat, self.lr, tab, self.skip_flag),
-                  work=4.0 * 6 * self.params_flat.numel(),
-                  keep=[s2 for (_, _, _, _, s2) in self.segments if s2 is not None])
+            self._emit_sgd(P)
         P.mark("end")
         for train, entries, prog in ((True, self._gpack_train, P), (False, self._gpack_frozen, prep)):
             for k, (a, lda, Kc, M, dst) in enumerate(entries):
@@ -665,16 +601,7 @@ class NativeResNetFPN(object):
             op.i[0] = len(entries)
             op.work = 8.0 * sum(Kc * M for (_, _, Kc, M, _) in entries)
         prep.build()
-        self.wss = {k: torch.empty(max(self._ws_need, 16), dtype=torch.uint8, device=dev) for k in self._wstreams}
-        self.ws = self.wss[self._wstreams[0]]
-        for idx, slot, k in self._ws_ops:
-            P.set_ptr(idx, slot, self.wss[k])
-        # the split-engine 3x3 launches of this network run one after the other on its stream: one workspace
-        self.split_ws = torch.empty(max(self._split_need, 16), dtype=torch.uint8, device=dev)
-        for idx in self._split_ops:
-            P.set_ptr(idx, 3, self.split_ws)
-        for idx in self._gemm_split_ops:
-            P.set_ptr(idx, 1, self.split_ws)
+        self._bind_workspaces()
         P.build()
 
     # -- forward ----------------------------------------------------------------------------------------
@@ -809,7 +736,8 @@ class NativeResNetFPN(object):
         # output convs: filter gradients and the three data gradients in one launch
         dt5, dt4, dt3 = self._like(t5), self._like(t4), self._like(t3)
         if L["out.0"].engine == Engine.SPLIT:
-            self._measure(P, [d5, d4, d3], D)          # one pass for the three filter gradients and the data gradient
+            # one pass for the three filter gradients and the data gradient
+            self._amax.measure(P, [[d5], [d4], [d3]], D)
         for t, d, name in ((t5, d5, "out.0"), (t4, d4, "out.1"), (t3, d3, "out.2")):
             self._wgrad3(P, t, d, L[name])
         self._conv3(P, [(d, dt, None, L[name].pd, None)

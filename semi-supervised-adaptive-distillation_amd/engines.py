@@ -1,6 +1,8 @@
 """Which engine runs a 3x3 convolution of the native fp32 pipelines (head_pipeline.DistillHeads,
-backbone_pipeline.NativeResNetFPN): the engine type, the one read of the environment switches, the rule of each
-pipeline, and the two tables (ssad_pack_entry[], ssad_conv_level[]) both pipelines hand to the kernels.
+backbone_pipeline.NativeResNetFPN): the engine type, the one read of the environment switches, the rules of each
+pipeline, the two tables (ssad_pack_entry[], ssad_conv_level[]) both pipelines hand to the kernels, the table of
+|max| words of the split-operand engines (AmaxTable) and the one emitter of each 3x3 launch record (emit_conv3x3,
+emit_conv3x3_wgrad).
 
 A pipeline reads the switches once, at construction, asks the rule for every convolution before it allocates
 anything, packs each filter in the layout of the planned engine and launches the planned engine on it.  DESIGN.md
@@ -9,6 +11,8 @@ section 3.7a has the rules as tables.
 import collections
 import enum
 import os
+
+import torch
 
 from . import kernels as K
 from . import program as PR
@@ -117,6 +121,18 @@ def backbone_engine(sw, train, cout, cin):
     return Engine.F22
 
 
+def subnet_wgrad_split(sw, cout, cin):
+    """A subnet filter gradient on the split-operand engine (conv3x3_wgrad_split.hip)?  SSAD_SPLIT_CONV bit 32
+    (default): the >= 128-wide ones (towers, cls_pred)."""
+    return bool(sw.split_conv & 32) and cout >= 128 and cin >= 64
+
+
+def backbone_wgrad_split(sw, cout, cin):
+    """A backbone 3x3 filter gradient on the split-operand engine?  SSAD_SPLIT_CONV bit 64 (default): the >= 256-wide
+    ones (the 128-wide res3 layers are level with the F(3x3, 2x2) engine there: 2 blocks of dW, 128 slabs to reduce)."""
+    return bool(sw.split_conv & 64) and cout >= 256 and cin >= 256
+
+
 def same_engine(engines):
     """The one engine of a launch; problems planned on different engines cannot share one."""
     engines = set(engines)
@@ -150,3 +166,95 @@ def emit_packs(P, klass, packs, order):
                 tab[k] = K.PackEntry(w.data_ptr(), cout, cin, *[t.data_ptr() if t is not None else 0 for t in (pf, pd)])
             P.add(PR.WINO_PACK_FILTERS, klass, i=(len(entries), _PACK_LAYOUT[engine]), p=(tab,), work=sum(moved),
                   keep=[t for w, _, _, pf, pd in entries for t in (w, pf, pd) if t is not None])
+
+
+class AmaxTable(object):
+    """The |max| words of one pipeline's split-operand engines: `tensor` (int32, zeroed by the pipeline's ONE fill at
+    the start of its forward segment), the next free word and {tensor addresses: word}.  A stale or unwritten word is
+    a wrong power-of-two scale, so: a launch's words are one block of consecutive words in its operand order; the
+    block is found again by the whole group list, by each group and -- where a group is one tensor -- by the tensor
+    (a filter gradient reads one tower's levels, or one tensor, of the launch that produced or first read them); a
+    tensor nobody folded is measured once, on the main stream, in front of its first reader, and a later reader on an
+    auxiliary stream is handed the word.  Tensors go by address: every activation / gradient buffer of a program is
+    allocated once and written once per step before its readers."""
+
+    def __init__(self, words, device):
+        self.words, self.next, self.word = words, 0, {}
+        self.tensor = torch.zeros(words, dtype=torch.int32, device=device)
+
+    def addr(self, k):
+        return self.tensor.data_ptr() + 4 * k
+
+    def find(self, groups):
+        return self.word.get(tuple(t.data_ptr() for g in groups for t in g))
+
+    def reserve(self, groups):
+        """First word of a fresh block for groups = [[tensor]]: their PRODUCER's epilogue folds the |max| in, or
+        measure() writes them.  (The freshest words serve later readers.)"""
+        base = k = self.next
+        self.next += sum(len(g) for g in groups)
+        if self.next > self.words:
+            raise K.KernelError("|max| table full")
+        self.word[tuple(t.data_ptr() for g in groups for t in g)] = base
+        for g in groups:
+            self.word[tuple(t.data_ptr() for t in g)] = k
+            k += len(g)
+        return base
+
+    def measure(self, P, groups, channels, table=None, field=0):
+        """First word of the groups' block: found, or measured here on the main stream into a fresh block -- through
+        `table` (the reading launch's own ssad_conv_level[], field 0 = x, 1 = aux), else one tensor by SPLIT_ABSMAX
+        and several through a level table of their own."""
+        base = self.find(groups)
+        if base is None:
+            base = self.reserve(groups)
+            ts = [t for g in groups for t in g]
+            nbytes = 4.0 * sum(t.numel() for t in ts)
+            if table is None and len(ts) == 1:
+                P.add(PR.SPLIT_ABSMAX, 73, p=(ts[0], self.addr(base)), l=(ts[0].numel(),), work=nbytes, stream=0)
+            else:
+                if table is None:
+                    table, field = conv_table([(t, None, None, None, None) for t in ts]), 0
+                P.add(PR.SPLIT_ABSMAX_LEVELS, 73, i=(len(ts), channels, field), p=(table, self.addr(base)),
+                      work=nbytes, keep=ts, stream=0)
+        return base
+
+
+def emit_conv3x3(P, klass, rows, cout, cin, flags, engine, amax, ws, levels=1, own_table=False, fold=True):
+    """One CONV3X3 record: independent convolutions of one (cout, cin) on one engine.  rows: conv_table()'s, `levels`
+    consecutive rows per problem.  The split-operand engine takes its workspace `ws`, the words of its inputs (found
+    or measured: through its own table when own_table) and, when fold, fresh words its epilogue folds the outputs'
+    |max| into.  -> (record index, table)"""
+    arr = conv_table(rows)
+    ptrs, sizes = (arr, None, None), ()
+    if engine == Engine.SPLIT:
+        nb = K.lib().ssad_conv3x3_split_workspace_bytes(arr, len(arr), cin)
+        groups = lambda f: [[r[f] for r in rows[k:k + levels]] for k in range(0, len(rows), levels)]
+        xa = amax.addr(amax.measure(P, groups(0), cin, arr if own_table else None))
+        ya = amax.addr(amax.reserve(groups(1))) if fold else None
+        ptrs, sizes = (arr, None, None, ws.need(nb), xa, ya), (nb,)
+    px = sum(r[0].shape[0] * r[0].shape[2] * r[0].shape[3] for r in rows)
+    return P.add(PR.CONV3X3, klass, i=(len(arr), cout, cin, flags, engine), l=sizes, p=ptrs,
+                 work=2.0 * 9 * cout * cin * px, keep=[t for r in rows for t in r if t is not None]), arr
+
+
+def emit_conv3x3_wgrad(P, klasses, xs, dys, gw, gb, cout, cin, split, amax, fork, own_table=False):
+    """One CONV3X3_WGRAD record over the levels xs / dys that share the filter gradient gw (+ bias gradient gb).
+    split: the pipeline's rule wants the split-operand engine (a level of 2 GiB or more still goes to the exact
+    one); klasses = (exact, split) timing classes.  The operands' words are found or measured on the main stream;
+    then fork(P) emits the pipeline's fork and returns the record's (stream, Workspace).  -> (record index, table)"""
+    arr = conv_table([(x, None, dy, None, None) for x, dy in zip(xs, dys)])
+    L = K.lib()
+    nb = L.ssad_conv3x3_wgrad_split_workspace_bytes(arr, len(arr), cout, cin) if split else 0
+    split = nb > 0
+    xa = da = None
+    if split:
+        xa = amax.addr(amax.measure(P, [list(xs)], cin, arr if own_table else None, 0))
+        da = amax.addr(amax.measure(P, [list(dys)], cout, arr if own_table else None, 1))
+    else:
+        nb = L.ssad_conv3x3_wgrad_workspace_bytes(arr, len(arr), cout, cin)
+    stream, ws = fork(P)
+    px = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
+    return P.add(PR.CONV3X3_WGRAD, klasses[split], i=(len(arr), cout, cin, 0, int(split)), l=(nb,),
+                 p=(arr, gw, gb, ws.need(nb), xa, da), work=2.0 * 9 * cout * cin * px, keep=list(xs) + list(dys),
+                 stream=stream), arr

@@ -34,7 +34,8 @@ from . import kernels as K
 from . import program as PR
 from . import synth
 from .data_parallel import BucketedAllReduce
-from .engines import Engine, Switches, conv_table, emit_packs, filter_floats, same_engine, subnet_engine
+from .engines import (AmaxTable, Engine, Switches, emit_conv3x3, emit_conv3x3_wgrad, emit_packs, filter_floats,
+                      same_engine, subnet_engine, subnet_wgrad_split)
 from .modeling.retinanet_heads import HeadConfig, retinanet_bias_init
 
 
@@ -126,7 +127,6 @@ class DistillHeads(object):
         self.teacher_bbox_tower = teacher_bbox_tower and self.distill
         self.switches = Switches.read().for_subnets(self.distill, self.F16)     # the one read of the engine switches
         self.split_conv = self.switches.split_conv
-        self._split_ops, self._split_ws_need = [], 0
         self.momentum, self.weight_decay = momentum, weight_decay
         self.pg, self.world_size = process_group, world_size
         self.dp = BucketedAllReduce(process_group, world_size)
@@ -223,48 +223,16 @@ class DistillHeads(object):
 
     # -- program construction ---------------------------------------------------------
     @staticmethod
-    def _conv_table(problems):
+    def _rows(problems):
         """problems: [(xs, outs or None, masks or None, packed or None, bias or None)], one tensor per level in xs / outs /
-        masks -> ssad_conv_level[], the problems' levels one after the other"""
-        return conv_table([(x, outs[l] if outs is not None else None, masks[l] if masks is not None else None, packed, bias)
-                           for xs, outs, masks, packed, bias in problems for l, x in enumerate(xs)])
+        masks -> engines.conv_table()'s rows, the problems' levels one after the other"""
+        return [(x, outs[l] if outs is not None else None, masks[l] if masks is not None else None, packed, bias)
+                for xs, outs, masks, packed, bias in problems for l, x in enumerate(xs)]
 
-    # -- |max| words of the split-operand engines (as backbone_pipeline._measure / _produces) ------------------------
-    # One table per pipeline, zeroed by one fill at the start of the forward segment.  A launch's words are one
-    # contiguous block in its problem order; the level list of every problem is registered too, so that a filter
-    # gradient (one tower's five levels) finds the words of the launch that produced or first read its tensors.
-    # Every activation / gradient buffer of the subnets is written by exactly one launch per step.
+    # |max| words of the split-operand engines (engines.AmaxTable): a launch's block holds its problems' level lists one
+    # after the other, so that a filter gradient (one tower's levels) finds the words of the launch that produced or
+    # first read its tensors; a reader measures through its own level table.
     AMAX_WORDS = 2048
-
-    def _amax_block(self, lists):
-        n = sum(len(l) for l in lists)
-        base = self._amax_next
-        self._amax_next += n
-        if self._amax_next > self.AMAX_WORDS:
-            raise K.KernelError("|max| table full")
-        self._amax_groups[tuple(t.data_ptr() for l in lists for t in l)] = base
-        k = base
-        for l in lists:
-            self._amax_groups[tuple(t.data_ptr() for t in l)] = k
-            k += len(l)
-        return base
-
-    def _amax_addr(self, base):
-        return self.amax.data_ptr() + 4 * base
-
-    def _amax_known(self, lists):
-        return self._amax_groups.get(tuple(t.data_ptr() for l in lists for t in l))
-
-    def _amax_measure(self, P, arr, lists, channels, field=0):
-        """Words of the tensors a launch reads (its level table's field 0 = x, 1 = aux): found, or measured here on
-        the main stream into a fresh block."""
-        base = self._amax_known(lists)
-        if base is None:
-            base = self._amax_block(lists)
-            n = sum(len(l) for l in lists)
-            P.add(PR.SPLIT_ABSMAX_LEVELS, 73, i=(n, channels, field), p=(arr, self._amax_addr(base)),
-                  work=4.0 * sum(t.numel() for l in lists for t in l), keep=[t for l in lists for t in l], stream=0)
-        return base
 
     # timing class of a launch by (role, engine); "teacher_...": a launch of the teacher's problems alone.  The direct
     # engine has one class for every role (18).
@@ -278,25 +246,10 @@ class DistillHeads(object):
              ("tower_dgrad", Engine.F22): 16, ("tower_dgrad", Engine.F24): 24, ("tower_dgrad", Engine.SPLIT): 29}
 
     def _emit_conv(self, P, problems, Cout, Cin, flags, role, engine, teacher=False):
-        """One launch of independent convolutions of equal (Cout, Cin) on one engine (the split-operand engine's
-        workspace is bound by _finish_workspaces)."""
-        arr = self._conv_table(problems)
-        px = sum(x.shape[0] * x.shape[2] * x.shape[3] for p in problems for x in p[0])
+        """One launch of independent convolutions of equal (Cout, Cin) on one engine; every output's |max| is folded."""
         klass = 18 if engine == Engine.DIRECT else self.KLASS[("teacher_" if teacher else "") + role, engine]
-        ptrs, sizes = (arr, None, None), ()
-        if engine == Engine.SPLIT:
-            nb = K.lib().ssad_conv3x3_split_workspace_bytes(arr, len(arr), Cin)
-            self._split_ws_need = max(self._split_ws_need, nb)
-            xa = self._amax_addr(self._amax_measure(P, arr, [list(p[0]) for p in problems], Cin))
-            ya = self._amax_addr(self._amax_block([list(p[1]) for p in problems]))     # folded in by the epilogue
-            ptrs, sizes = (arr, None, None, None, xa, ya), (nb,)
-        idx = P.add(PR.CONV3X3, klass, i=(len(arr), Cout, Cin, flags, engine), l=sizes, p=ptrs,
-                    work=2.0 * 9 * Cout * Cin * px,
-                    keep=[t for p in problems for t in (list(p[0]) + list(p[1] or []) + list(p[2] or []))
-                          ] + [t for p in problems for t in p[3:] if t is not None])
-        if engine == Engine.SPLIT:
-            self._split_ops.append((P, idx))
-        return idx, arr
+        return emit_conv3x3(P, klass, self._rows(problems), Cout, Cin, flags, engine, self._amax, self._split,
+                            levels=len(self.shapes), own_table=True)
 
     def _emit_group(self, P, probs, role, flags, bind=False):
         """probs: [(who, layer, problem)], forward convolutions that may share launches: one launch per (Cout, Cin,
@@ -317,29 +270,16 @@ class DistillHeads(object):
                 self._in_slots.extend((arr, k, w, l) for k, (w, l) in enumerate(slots))
 
     def _emit_wgrad(self, P, xs, dys, name, Cout, klass):
-        arr = self._conv_table([(xs, None, dys, None, None)])
-        # SSAD_SPLIT_CONV bit 32 (default): the >= 128-wide filter gradients on the split-operand engine
-        split = bool(self.switches.split_conv & 32) and Cout >= 128 and self.D >= 64
-        if split and not K.lib().ssad_conv3x3_wgrad_split_workspace_bytes(arr, len(arr), Cout, self.D):
-            split = False           # (a level of 2 GiB or more: the exact engine)
-        size_fn = K.lib().ssad_conv3x3_wgrad_split_workspace_bytes if split else K.lib().ssad_conv3x3_wgrad_workspace_bytes
-        nb = size_fn(arr, len(arr), Cout, self.D)
-        self._wgrad_ws_need = max(getattr(self, "_wgrad_ws_need", 0), nb)
-        px = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
-        xa = da = None
-        if split:                       # (on the main stream, before the fork)
-            xa = self._amax_addr(self._amax_measure(P, arr, [list(xs)], self.D, 0))
-            da = self._amax_addr(self._amax_measure(P, arr, [list(dys)], Cout, 1))
+        exact = 19 if self.fwd_engine["student", name] == Engine.DIRECT else klass
+        return emit_conv3x3_wgrad(P, (exact, {5: 68, 6: 69}.get(klass, klass)), xs, dys, self.grads[name + "_w"],
+                                  self.grads[name + "_b"], Cout, self.D, subnet_wgrad_split(self.switches, Cout, self.D),
+                                  self._amax, self._fork, own_table=True)
+
+    def _fork(self, P):
+        """The filter gradients' stream and workspace, behind everything enqueued so far (the producer of dys)."""
         if self._wstream:
-            P.fork(self._wstream)       # behind everything enqueued so far (the producer of dys)
-        if split:
-            klass = {5: 68, 6: 69}.get(klass, klass)
-        idx = P.add(PR.CONV3X3_WGRAD, 19 if self.fwd_engine["student", name] == Engine.DIRECT else klass,
-                    i=(len(arr), Cout, self.D, 0, 1 if split else 0), l=(nb,),
-                    p=(arr, self.grads[name + "_w"], self.grads[name + "_b"], None, xa, da),
-                    work=2.0 * 9 * Cout * self.D * px, keep=list(xs) + list(dys), stream=self._wstream)
-        self._wgrad_ops.append(idx)
-        return idx, arr
+            P.fork(self._wstream)
+        return self._wstream, self._wgrad
 
     PACK_ORDER = (Engine.SPLIT, Engine.F24, Engine.F22, Engine.DIRECT)
 
@@ -369,9 +309,11 @@ class DistillHeads(object):
         # filter gradients on an auxiliary stream beside the data-gradient chain (program.py FORK / JOIN)
         ov = self._overlap_wgrad
         self._wstream = 1 if (os.environ.get("SSAD_OVERLAP_WGRAD", "1") == "1" if ov is None else ov) else 0
-        self._wgrad_ops, self._wgrad_ws_need = [], 0
-        self.amax = torch.zeros(self.AMAX_WORDS, dtype=torch.int32, device=self.device)
-        self._amax_groups, self._amax_next = {}, 0
+        # one workspace for the split-engine convolutions (they run one after the other on the program's stream), one
+        # for the filter gradients
+        self._split, self._wgrad = PR.Workspace(), PR.Workspace()
+        self._amax = AmaxTable(self.AMAX_WORDS, self.device)
+        self.amax = self._amax.tensor
         self._in_slots = []          # (table, index, which): entries that read the bound inputs
         # filters (the teacher's are frozen: packed by a program of their own, run when they change)
         self.packed, s_packs = self._alloc_packed(self.params, "student")
@@ -401,17 +343,8 @@ class DistillHeads(object):
             Q = self.prog_distill_only = PR.Program()
             self._emit_losses(Q, supervised=False)
             Q.build()
-        self._finish_workspaces(P)
+        self.split_ws, self.wgrad_ws = self._split.bind(self.device), self._wgrad.bind(self.device)
         P.build()
-
-    def _finish_workspaces(self, P):
-        # one workspace for every split-engine convolution: they run one after the other on the program's stream
-        self.split_ws = torch.empty(max(self._split_ws_need, 16), dtype=torch.uint8, device=self.device)
-        for prog, idx in self._split_ops:
-            prog.set_ptr(idx, 3, self.split_ws)
-        self.wgrad_ws = torch.empty(max(self._wgrad_ws_need, 16), dtype=torch.uint8, device=self.device)
-        for idx in self._wgrad_ops:
-            P.set_ptr(idx, 3, self.wgrad_ws)
 
     # -- forward --------------------------------------------------------------------------
     def _emit_forward(self, P):
@@ -902,19 +835,11 @@ class DistillHeadsF16(DistillHeads):
             arr[l].x, arr[l].dy = xb.data_ptr(), dyb.data_ptr()
             arr[l].N, arr[l].H, arr[l].W = xb.shape[0], xb.shape[2], xb.shape[3]
         nb = K.lib().ssad_conv3x3_wgrad_f16_levels_workspace_bytes(arr, n, Cin, Cout)
-        self._wgrad_ws_need = max(self._wgrad_ws_need, nb)
         px = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xbs)
-        if self._wstream:
-            P.fork(self._wstream)
-        idx = P.add(PR.F16_WGRAD, 37, i=(n, Cin, Cout, 0), f=(1.0,), l=(nb,),
-                    p=(arr, self.ls_state[1:2], self.grads[name + "_w"], self.grads[name + "_b"], None),
-                    work=2.0 * 9 * Cout * Cin * px, keep=list(xbs) + list(dybs), stream=self._wstream)
-        self._wgrad_ops.append(idx)
-
-    def _finish_workspaces(self, P):
-        self.wgrad_ws = torch.empty(max(self._wgrad_ws_need, 16), dtype=torch.uint8, device=self.device)
-        for idx in self._wgrad_ops:
-            P.set_ptr(idx, 4, self.wgrad_ws)
+        stream, ws = self._fork(P)
+        P.add(PR.F16_WGRAD, 37, i=(n, Cin, Cout, 0), f=(1.0,), l=(nb,),
+              p=(arr, self.ls_state[1:2], self.grads[name + "_w"], self.grads[name + "_b"], ws.need(nb)),
+              work=2.0 * 9 * Cout * Cin * px, keep=list(xbs) + list(dybs), stream=stream)
 
     def _emit_backward(self, P):
         cfg, D = self.cfg, self.D

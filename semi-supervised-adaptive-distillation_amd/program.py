@@ -215,6 +215,25 @@ class Timing(object):
             pass
 
 
+class Workspace(object):
+    """Scratch memory shared by launches that run one after the other on one stream.  A launch is emitted with
+    `ws.need(nbytes)` in its pointer slot: Program.add notes (program, record, slot) here, and bind() allocates the
+    largest need once and fills every noted slot.  The pipeline owns the tensor; it is in no Program.keep."""
+
+    def __init__(self):
+        self.nbytes, self.slots = 0, []
+
+    def need(self, nbytes):
+        self.nbytes = max(self.nbytes, int(nbytes))
+        return self
+
+    def bind(self, device):
+        tensor = torch.empty(max(self.nbytes, 16), dtype=torch.uint8, device=device)
+        for prog, index, slot in self.slots:
+            prog.set_ptr(index, slot, tensor)
+        return tensor
+
+
 class Program(object):
     def __init__(self):
         self.ops = []
@@ -245,8 +264,11 @@ class Program(object):
         for k, v in enumerate(l):
             o.l[k] = int(v)
         for k, v in enumerate(p):
-            o.p[k] = _addr(v)
-        self.keep.extend([v for v in p if v is not None and not isinstance(v, int)])
+            if isinstance(v, Workspace):
+                v.slots.append((self, len(self.ops), k))        # NULL until Workspace.bind()
+            else:
+                o.p[k] = _addr(v)
+        self.keep.extend([v for v in p if v is not None and not isinstance(v, (int, Workspace))])
         self.keep.extend(keep)
         self.ops.append(o)
         self.arr = None

@@ -171,6 +171,18 @@ def _env(**env):
                 os.environ[k] = v
 
 
+@contextlib.contextmanager
+def _gemm_split_min_pixels(n):
+    """backbone_pipeline.GEMM_SPLIT_MIN_PIXELS = n around a build: at 128 x 128, N = 1 the default keeps every
+    pointwise layer off the split-operand route."""
+    from ssad_amd import backbone_pipeline as BP
+    saved, BP.GEMM_SPLIT_MIN_PIXELS = BP.GEMM_SPLIT_MIN_PIXELS, n
+    try:
+        yield
+    finally:
+        BP.GEMM_SPLIT_MIN_PIXELS = saved
+
+
 def _matrix():
     return [dict(SSAD_SPLIT_CONV=s, SSAD_STUDENT_F24=f, SSAD_TEACHER_F24=t)
             for s in (0, 3, 15, 47, 511) for f in (0, 1, 3, 7, 15) for t in (0, 1, 2)]
@@ -187,11 +199,18 @@ def configurations():
     from ssad_amd.head_pipeline import DistillHeads, DistillHeadsF16
     from ssad_amd.modeling.retinanet_heads import HeadConfig
 
-    def heads(cls=DistillHeads, cfg=None, **kw):
-        return lambda: [cls(cfg or HeadConfig(num_gpus=1), N=1, shapes=SHAPES, device="cpu", **kw)]
+    def heads(cls=DistillHeads, cfg=None, shapes=SHAPES, **kw):
+        return lambda: [cls(cfg or HeadConfig(num_gpus=1), N=1, shapes=shapes, device="cpu", **kw)]
 
-    def backbone(arch="r50", **kw):
-        return lambda: [NativeResNetFPN(arch, 1, (128, 128), "cpu", **kw)]
+    def backbone(arch="r50", cls=NativeResNetFPN, **kw):
+        return lambda: [cls(arch, 1, (128, 128), "cpu", **kw)]
+
+    def pointwise(arch="r50", **kw):
+        """The pointwise layers on the split-operand route (GEMM_CONV_SPLIT, split CONV1X1_WGRAD)."""
+        def build():
+            with _gemm_split_min_pixels(0):
+                return backbone(arch, **kw)()
+        return build
 
     def f16_pair():
         shapes = [(16, 16), (8, 8), (4, 4), (2, 2), (1, 1)]
@@ -225,6 +244,21 @@ def configurations():
     out.append(("x101_64x4d_frozen", {}, backbone("x101-64x4d", train=False)))
     out.append(("r50_strided_winograd_train", dict(SSAD_STRIDED_3X3="winograd"), backbone(train=True)))
     out.append(("f16_pair", {}, f16_pair))
+    for bits in (511, 255):
+        out.append(("r50_pointwise_split%d_train" % bits, dict(SSAD_SPLIT_CONV=bits), pointwise(train=True)))
+    for arch in ("r50", "r101", "x101-64x4d"):
+        out.append(("%s_pointwise_split511_frozen" % arch.replace("-", "_"), dict(SSAD_SPLIT_CONV=511),
+                    pointwise(arch, train=False)))
+    # one level: a launch's whole key and its per-problem key coincide in the |max| word table
+    for distill in (True, False):
+        out.append(("heads_one_level_%s" % ("distill" if distill else "plain"), {},
+                    heads(shapes=[(5, 7)], distill=distill)))
+    # without the auxiliary streams, and the fp16 backbone without the heads' hand-over
+    out.append(("r50_no_overlap_wgrad_train", {}, backbone(train=True, overlap_wgrad=False)))
+    out.append(("heads_f16_no_overlap_wgrad", {}, heads(cls=DistillHeadsF16, overlap_wgrad=False)))
+    out.append(("f16_r50_own_io_train", {}, backbone(cls=NativeResNetFPNF16, train=True)))
+    out.append(("f16_r50_own_io_no_overlap_wgrad_train", {},
+                backbone(cls=NativeResNetFPNF16, train=True, overlap_wgrad=False)))
     return out
 
 
