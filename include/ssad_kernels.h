@@ -574,7 +574,9 @@ SSAD_API int ssad_conv1x1_gemm(const ssad_gemm_conv* desc_host, ssad_stream_t st
  * it exists); a is split into the workspace.  Any K, M, P; tensors below 2 GiB (SSAD_E_BADARG otherwise: use
  * ssad_conv1x1_gemm).  workspace: ssad_conv1x1_gemm_split_workspace_bytes(desc) bytes; the call = |max| pass + split of
  * a + the GEMM on `stream`.  Pays on the compute-bound layers (K >= 256, M >= 256: res4, res5, the laterals); the
- * HBM-bound ones stay on ssad_conv1x1_gemm. */
+ * HBM-bound ones stay on ssad_conv1x1_gemm.  With M a multiple of 8 the GEMM kernel's instance has residual / mask /
+ * accumulate compiled in (bit-identical results); SSAD_GEMM_FLY_GENERIC=1 in the environment, read at every launch,
+ * forces the all-runtime instance that serves every other M. */
 SSAD_API size_t ssad_conv1x1_gemm_split_workspace_bytes(const ssad_gemm_conv* desc_host);
 SSAD_API int ssad_conv1x1_gemm_split(const ssad_gemm_conv* desc_host, void* workspace, size_t workspace_bytes,
                                      ssad_stream_t stream);

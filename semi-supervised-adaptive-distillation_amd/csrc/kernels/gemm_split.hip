@@ -107,6 +107,9 @@ __global__ __launch_bounds__(kThreads) void gsplit_pack_multi_kernel(const GPack
 #ifndef GFLY_ABLATE    // debug builds (results wrong): 1 no fetch in the loop, 2 no split / LDS write, 4 one product, 8 no MFMA
 #define GFLY_ABLATE 0
 #endif
+#ifndef GFLY_PREFETCH  // 0 (A/B builds): the fast instances issue their epilogue's first loads behind the last chunk
+#define GFLY_PREFETCH 1
+#endif
 constexpr int FKC = 32;                             // channels per chunk (2 MFMA steps)
 constexpr int FWG = 512;
 constexpr int F_XP = (FKC / 8) * PT * 16;           // bytes of one x plane of a stage (8 KB)
@@ -127,6 +130,26 @@ struct FArgs {
   int ptiles, mblocks, items;
 };
 
+// One output's epilogue sequence.  Every instance of the kernel goes through this one function, so that all of them
+// round alike: scale(s) and bias, + residual, ReLU, mask select, + old value.  (m1, m2) = (1, sc1) gives
+// fmaf(a, sc1, b) bit for bit; (sc1, sc2) is the two-scale form a * sc1 * sc2 + b as hipcc contracts it.
+__device__ __forceinline__ float fly_finish(float a, float m1, float m2, float b, float rs, bool relu, bool has_mask,
+                                            float mk, float old) {
+  float v = fmaf(a * m1, m2, b);
+  v += rs;
+  if (relu) v = fmaxf(v, 0.0f);
+  if (has_mask) v = mk > 0.0f ? v : 0.0f;
+  v += old;
+  return v;
+}
+
+// The epilogue's options are template constants: residual, mask and accumulation each cost sixteen loads per lane and
+// block when present and nothing when absent, and with M a multiple of 8 an 8-channel group lies inside M or outside
+// it as a whole.  As runtime values they cost every one of a lane's 64 outputs a chain of scalar compares and three
+// branches around the three loads, with a full wait behind each load.  RAGGED is the all-runtime form (the options
+// are read from q and RES / MASK / ACC are ignored): it serves M & 7 != 0, where a lane's two half-groups of four
+// channels end at different places, and is what SSAD_GEMM_FLY_GENERIC=1 forces for every call.
+template <bool RES, bool MASK, bool ACC, bool RAGGED>
 __global__ __launch_bounds__(FWG, 1) void gemm_fly_kernel(const FArgs q) {
   extern __shared__ __attribute__((aligned(16))) char flds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -231,7 +254,7 @@ __global__ __launch_bounds__(FWG, 1) void gemm_fly_kernel(const FArgs q) {
   put(flds);
   fetch(1);
   __syncthreads();
-  for (int c = 0; c < nchunks; ++c) {
+  auto chunk = [&](int c, auto&& before_second_step) {
     const char* stage = flds + (c & 1) * F_STAGE;
     char* other = flds + ((c & 1) ^ 1) * F_STAGE;
     __builtin_amdgcn_sched_barrier(0);
@@ -240,9 +263,13 @@ __global__ __launch_bounds__(FWG, 1) void gemm_fly_kernel(const FArgs q) {
     __builtin_amdgcn_sched_barrier(0);
     if (!(GFLY_ABLATE & 1)) fetch(c + 2);
     __builtin_amdgcn_sched_barrier(0);
+    before_second_step();
     step(stage, 1);
     __syncthreads();
-  }
+  };
+  // (the fast instances run their last chunk below, with the epilogue's first loads in front of its second step)
+  constexpr bool kPrefetch = GFLY_PREFETCH && !RAGGED;
+  for (int c = 0; c < nchunks - (kPrefetch ? 1 : 0); ++c) chunk(c, [] {});
 
   // ---- epilogue: C/D row = (r & 3) + 8 (r >> 2) + 4 h, column = j
   const int oc_w = ocb + wm * 64;
@@ -261,44 +288,104 @@ __global__ __launch_bounds__(FWG, 1) void gemm_fly_kernel(const FArgs q) {
   const __amdgpu_buffer_rsrc_t rrs = uniform_rsrc(q.residual ? (const void*)q.residual : (const void*)q.y, q.residual ? ybytes : 0u);
   const __amdgpu_buffer_rsrc_t mrs = uniform_rsrc(q.mask ? (const void*)q.mask : (const void*)q.y, q.mask ? ybytes : 0u);
   const __amdgpu_buffer_rsrc_t brs = uniform_rsrc(q.bias ? (const void*)q.bias : (const void*)q.y, q.bias ? (unsigned)M * 4u : 0u);
-  const bool relu = q.relu, has_res = q.residual != nullptr, has_mask = q.mask != nullptr, accum = q.accumulate;
-  const bool ragged = (M & 7) != 0;
+  const float m1 = one_scale ? sc2 : sc1, m2 = one_scale ? sc1 : sc2;    // fly_finish
+  const bool relu = q.relu;
   unsigned ymax = 0;
+  if constexpr (RAGGED) {
+    const bool has_res = q.residual != nullptr, has_mask = q.mask != nullptr, accum = q.accumulate;
+    const bool ragged = (M & 7) != 0;
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int oc0 = oc_w + i * 32;
-    float4 bq[4];
+    for (int i = 0; i < 2; ++i) {
+      const int oc0 = oc_w + i * 32;
+      float4 bq[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
-      bq[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(brs, (unsigned)h * 16u, (oc0 + 8 * g) * 4, 0));
+      for (int g = 0; g < 4; ++g)
+        bq[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(brs, (unsigned)h * 16u, (oc0 + 8 * g) * 4, 0));
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      float rs[16], mk[16], old[16];
+      for (int tt = 0; tt < 2; ++tt) {
+        float rs[16], mk[16], old[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ch = oc0 + 8 * (r >> 2) + (r & 3);
-        const unsigned vo = (ch < M && (!ragged || ch + 4 * h < M)) ? pvo[tt] : kOob;
-        rs[r] = has_res ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, vo, ch * P4, 0)) : 0.0f;
-        mk[r] = has_mask ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, vo, ch * P4, 0)) : 1.0f;
-        old[r] = accum ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yrs, vo, ch * P4, 0)) : 0.0f;
-      }
+        for (int r = 0; r < 16; ++r) {
+          const int ch = oc0 + 8 * (r >> 2) + (r & 3);
+          const unsigned vo = (ch < M && (!ragged || ch + 4 * h < M)) ? pvo[tt] : kOob;
+          rs[r] = has_res ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, vo, ch * P4, 0)) : 0.0f;
+          mk[r] = has_mask ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, vo, ch * P4, 0)) : 1.0f;
+          old[r] = accum ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yrs, vo, ch * P4, 0)) : 0.0f;
+        }
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (oc0 + 8 * g >= M) continue;               // wave-uniform
+        for (int g = 0; g < 4; ++g) {
+          if (oc0 + 8 * g >= M) continue;               // wave-uniform
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          float v = one_scale ? fmaf(acc[i][tt][r], sc1, bq[g][e]) : acc[i][tt][r] * sc1 * sc2 + bq[g][e];
-          v += rs[r];
-          if (relu) v = fmaxf(v, 0.0f);
-          if (has_mask) v = mk[r] > 0.0f ? v : 0.0f;
-          v += old[r];
-          const unsigned vo = (!ragged || oc0 + 8 * g + 4 * h + e < M) ? pvo[tt] : kOob;
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, vo, (oc0 + 8 * g + e) * P4, 0);
-          const unsigned av = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
-          if (vo != kOob) ymax = ymax > av ? ymax : av;
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g + e;
+            const float v = fly_finish(acc[i][tt][r], m1, m2, bq[g][e], rs[r], relu, has_mask, mk[r], old[r]);
+            const unsigned vo = (!ragged || oc0 + 8 * g + 4 * h + e < M) ? pvo[tt] : kOob;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, vo, (oc0 + 8 * g + e) * P4, 0);
+            const unsigned av = __builtin_bit_cast(unsigned, v) & 0x7fffffffu;
+            if (vo != kOob) ymax = ymax > av ? ymax : av;
+          }
         }
       }
+    }
+  } else {
+    // A block b = 2 i + tt is the 32 channels from oc_w + 32 i by the 32 pixels of pvo[tt]; a lane holds 16 of its
+    // outputs, four per 8-channel group g.  A group at or past M is skipped wave-uniformly through its offset: kOob is
+    // or-ed into it (as a scalar word, so that no branch forms around the loads), loads from kOob and above return
+    // zero and stores there are dropped, exactly as for a pixel past the image.
+    unsigned gm[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) gm[i][g] = __builtin_amdgcn_readfirstlane(oc_w + i * 32 + 8 * g < M ? 0u : kOob);
+    float4 bq[2][4];
+    float rs[2][16], mk[2][16], old[2][16];
+    // the optional operands of block b into register set s, in the order in which finish() consumes them
+    auto issue = [&](int b, int s) {
+      const int oc0 = oc_w + (b >> 1) * 32;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int g = r >> 2, so = (oc0 + 8 * g + (r & 3)) * P4;
+        const unsigned vo = pvo[b & 1] | gm[b >> 1][g];
+        if constexpr (RES) rs[s][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, vo, so, 0));
+        if constexpr (MASK) mk[s][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, vo, so, 0));
+        if constexpr (ACC) old[s][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yrs, vo, so, 0));
+      }
+    };
+    auto finish = [&](int b, int s) {
+      const int i = b >> 1, tt = b & 1, oc0 = oc_w + i * 32;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int g = r >> 2, e = r & 3;
+        const unsigned vo = pvo[tt] | gm[i][g];
+        const float v = fly_finish(acc[i][tt][r], m1, m2, bq[i][g][e], RES ? rs[s][r] : 0.0f, relu, MASK,
+                                   MASK ? mk[s][r] : 1.0f, ACC ? old[s][r] : 0.0f);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, vo, (oc0 + 8 * g + e) * P4, 0);
+        const unsigned av = __builtin_bit_cast(unsigned, v) & (vo < kOob ? 0x7fffffffu : 0u);   // dropped: folds 0
+        ymax = ymax > av ? ymax : av;
+      }
+    };
+    // Every load is issued two blocks ahead of its use, back to back, and the waits are counted ones: block b + 2 is
+    // requested behind block b's stores, into the registers that block b has just released.
+    auto first_loads = [&] {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          bq[i][g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(brs, (unsigned)h * 16u,
+                                                                                    (oc_w + i * 32 + 8 * g) * 4, 0));
+      issue(0, 0);
+      issue(1, 1);
+    };
+    if constexpr (kPrefetch)
+      chunk(nchunks - 1, [&] { first_loads(); __builtin_amdgcn_sched_barrier(0); });
+    else
+      first_loads();
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      __builtin_amdgcn_sched_barrier(0);
+      finish(b, b & 1);
+      __builtin_amdgcn_sched_barrier(0);
+      if (b + 2 < 4) issue(b + 2, b & 1);
     }
   }
   if (q.amax_out) {                                  // one atomic per workgroup
@@ -508,6 +595,22 @@ int wpoint_plan(int N, int C, int P, int M, WPArgs* a) {
   return 0;
 }
 
+// SSAD_GEMM_FLY_GENERIC=1 sends every call to the all-runtime instance (A/B runs, the bit-identity test); read at
+// every launch.
+bool fly_generic_forced() {
+  const char* e = getenv("SSAD_GEMM_FLY_GENERIC");
+  return e && *e && atoi(e) != 0;
+}
+template <bool RES, bool MASK, bool ACC, bool RAGGED>
+void launch_fly(const FArgs& f, hipStream_t stream) {
+  static std::once_flag lds_once;           // > 64 KiB of dynamic LDS needs the opt-in, once per process and instance
+  std::call_once(lds_once, [] {
+    (void)hipFuncSetAttribute((const void*)gemm_fly_kernel<RES, MASK, ACC, RAGGED>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
+  });
+  hipLaunchKernelGGL((gemm_fly_kernel<RES, MASK, ACC, RAGGED>), dim3((unsigned)f.items), dim3(FWG), F_LDS, stream, f);
+}
+
 struct GPlan {
   size_t amax_off, a_off, total;
 };
@@ -620,11 +723,15 @@ int ssad_conv1x1_gemm_split_amax(const ssad_gemm_conv* d, const float* packed_a,
   const long long tiles = (long long)d->N * f.ptiles;
   if (tiles * f.mblocks >= (1LL << 30)) return SSAD_E_BADARG;
   f.items = (int)(cdiv((int)tiles, 8) * 8 * f.mblocks);
-  static std::once_flag lds_once;           // > 64 KiB of dynamic LDS needs the opt-in, once per process
-  std::call_once(lds_once, [&] {
-    (void)hipFuncSetAttribute((const void*)gemm_fly_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-  });
-  hipLaunchKernelGGL(gemm_fly_kernel, dim3((unsigned)f.items), dim3(FWG), F_LDS, stream, f);
+  const int form = (f.residual ? 4 : 0) | (f.mask ? 2 : 0) | (f.accumulate ? 1 : 0);
+  if ((d->M & 7) || fly_generic_forced()) launch_fly<false, false, false, true>(f, stream);
+  else if (form == 0) launch_fly<false, false, false, false>(f, stream);
+  else if (form == 1) launch_fly<false, false, true, false>(f, stream);
+  else if (form == 2) launch_fly<false, true, false, false>(f, stream);
+  else if (form == 3) launch_fly<false, true, true, false>(f, stream);
+  else if (form == 4) launch_fly<true, false, false, false>(f, stream);
+  else if (form == 6) launch_fly<true, true, false, false>(f, stream);
+  else return SSAD_E_BADARG;                // (accumulation onto a residual was refused above)
   return (int)hipGetLastError();
 }
 
