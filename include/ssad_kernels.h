@@ -298,6 +298,10 @@ SSAD_API int ssad_conv_pack_filter(
 #define SSAD_CONV_MASK_AUX 2  /* y = aux > 0 ? y : 0 (fused ReluGradient) */
 #define SSAD_CONV_SIGMOID 4   /* y = 1/(1+exp(-y)) (teacher cls_pred -> prob,
                                  caffe2/operators/sigmoid_op.cu:25-29 fused) */
+#define SSAD_CONV_ACCUM_AUX 32 /* F(2x4) engine only (ssad_conv3x3_forward_wino24), with SSAD_CONV_MASK_AUX and without
+                                * SSAD_CONV_RELU: y = aux > 0 ? y + acc : 0, acc = what y held before the launch (the
+                                * second data gradient into a ReLU output that two convolutions read); any other engine
+                                * refuses it (a program's CONV3X3 record: SSAD_E_BADARG) */
 #define SSAD_CONV_SPLIT_TAIL 8 /* Winograd F(2x2) engine only, a scheduling hint: split this launch's partial round
                                  even behind full rounds (ssad_conv_wino_split_tail setting 2 for one launch) -- for
                                  launches that have the chip to themselves, e.g. the subnets' forward pass */
@@ -460,6 +464,18 @@ SSAD_API int ssad_retinanet_anchor_labels(
     float* const* locs_out_host, float* const* targets_out_host, int capacity,
     int* counts_out, float* fg_bg_out, void* workspace, size_t workspace_bytes,
     ssad_stream_t stream);
+/* The same call with RETINANET.CLASS_SPECIFIC_BBOX (retinanet.py:140-151,288-293): class_specific_bbox = 1 writes
+ * column 1 of locs_out as 4 * (label - 1) + 4 * (num_classes - 1) * anchor, the first channel of the box of the
+ * anchor's class in a bbox_pred of 4 * (num_classes - 1) * A channels; labels, targets, counts and order are
+ * unchanged.  0 is ssad_retinanet_anchor_labels; any other value is SSAD_E_BADARG. */
+SSAD_API int ssad_retinanet_anchor_labels_ex(
+    const double* cell_anchors, int levels, int A, int k_min, const int* field_sizes_host,
+    const int* crop_h_host, const int* crop_w_host, const float* gt_boxes,
+    const int* gt_classes, const int* gt_counts, int N, int Gmax, int num_classes,
+    float positive_overlap, float negative_overlap, int* const* labels_out_host,
+    float* const* locs_out_host, float* const* targets_out_host, int capacity,
+    int* counts_out, float* fg_bg_out, void* workspace, size_t workspace_bytes,
+    ssad_stream_t stream, int class_specific_bbox);
 
 /* ---------------------------------------------------------------------- */
 /* Input blobs from uint8 images on the device                             */
@@ -791,6 +807,17 @@ SSAD_API int ssad_retinanet_detect_ex(
     float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
     int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
     const ssad_detect_post* post);
+/* ssad_retinanet_detect_ex for a RETINANET.CLASS_SPECIFIC_BBOX head: class_specific_bbox = 1 takes box_pred_host[l]
+ * as [1][A*4*C][H][W] and reads the four deltas of a candidate (anchor a, class c, y, x) from channels
+ * a*4*C + 4*c + k, the layout the training loss addresses (retnet_roi_fg_bbox_locs, roi_data/retinanet.py:140-151);
+ * 0 is ssad_retinanet_detect_ex; any other value is SSAD_E_BADARG.  Workspace: ssad_retinanet_detect_ex_workspace_bytes. */
+SSAD_API int ssad_retinanet_detect_class_specific(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
+    float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
+    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
+    const ssad_detect_post* post, int class_specific_bbox);
 
 /* COCO box evaluation on the device (detectron/lib/datasets/vid_eval.py: evaluateImg :236-318, accumulate
  * :320-425; driven for boxes by vid_dataset_evaluator.py:192-197).  useCats = 1, iouType 'bbox' only.

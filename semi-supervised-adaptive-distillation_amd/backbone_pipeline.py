@@ -973,9 +973,12 @@ class NativeDistillModel(object):
         Q = self.sum_prog = PR.Program()
         self._ptrs = []
         if not self.backbone_f16:
-            for a, b, d in zip(heads.d_fpn["cls"], heads.d_fpn["bbox"], self.student.d_fpn):
-                ptrs = (C.c_void_p * 2)(a.data_ptr(), b.data_ptr())
-                Q.add(PR.SUM_N, 51, i=(2,), l=(d.numel(),), p=(ptrs, d), work=12.0 * d.numel(), keep=[a, b, d])
+            # (a shared tower, HeadConfig.share_cls_bbox_tower: only the cls subnet reaches the FPN levels -- one term)
+            parts = [heads.d_fpn[t] for t in ("cls", "bbox") if t in heads.d_fpn]
+            for d, *terms in zip(self.student.d_fpn, *parts):
+                ptrs = (C.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
+                Q.add(PR.SUM_N, 51, i=(len(terms),), l=(d.numel(),), p=(ptrs, d), work=4.0 * (len(terms) + 1) * d.numel(),
+                      keep=terms + [d])
         Q.build()
         if self.f16:
             # mixed precision: the backbone's reduced gradients join the subnets' finiteness check

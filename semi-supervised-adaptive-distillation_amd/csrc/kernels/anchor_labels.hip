@@ -53,6 +53,7 @@ struct ALArgs {
   int T;                           // anchors per image
   float pos_thr, neg_thr;
   int num_classes;
+  int class_specific;              // RETINANET.CLASS_SPECIFIC_BBOX: column 1 of the fg list addresses the class's box
   // workspace
   float* a_max;                    // [N][T]
   int* a_arg;                      // [N][T]
@@ -241,7 +242,11 @@ __global__ __launch_bounds__(kCB) void al_scatter_kernel(const ALArgs p) {
   if (pos >= p.capacity) return;
   const Anchor b = anchor_of(p, t);
   float* loc = p.locs_out[l] + (long long)pos * 4;
-  loc[0] = (float)n; loc[1] = (float)(4 * b.a); loc[2] = (float)b.y; loc[3] = (float)b.x;
+  // retinanet.py:140-151,288-293: 4 * (label - 1) + 4 * (num_classes - 1) * anchor when class-specific
+  const int ch = p.class_specific
+                     ? 4 * ((int)p.label[(long long)n * p.T + t] - 1) + 4 * (p.num_classes - 1) * b.a
+                     : 4 * b.a;
+  loc[0] = (float)n; loc[1] = (float)ch; loc[2] = (float)b.y; loc[3] = (float)b.x;
   // boxes.py:193-224 with weights (1,1,1,1), float32
   const float* q = p.gt_boxes + ((long long)n * p.Gmax + p.a_arg[(long long)n * p.T + t]) * 4;
   const float ew = __fadd_rn(__fsub_rn(b.x2, b.x1), 1.0f), eh = __fadd_rn(__fsub_rn(b.y2, b.y1), 1.0f);
@@ -312,7 +317,21 @@ int ssad_retinanet_anchor_labels(
     float negative_overlap, int* const* labels_out_host, float* const* locs_out_host,
     float* const* targets_out_host, int capacity, int* counts_out, float* fg_bg_out,
     void* workspace, size_t workspace_bytes, ssad_stream_t stream) {
+  return ssad_retinanet_anchor_labels_ex(cell_anchors, levels, A, k_min, field_sizes_host, crop_h_host, crop_w_host,
+                                         gt_boxes, gt_classes, gt_counts, N, Gmax, num_classes, positive_overlap,
+                                         negative_overlap, labels_out_host, locs_out_host, targets_out_host, capacity,
+                                         counts_out, fg_bg_out, workspace, workspace_bytes, stream, 0);
+}
+
+int ssad_retinanet_anchor_labels_ex(
+    const double* cell_anchors, int levels, int A, int k_min, const int* field_sizes_host,
+    const int* crop_h_host, const int* crop_w_host, const float* gt_boxes, const int* gt_classes,
+    const int* gt_counts, int N, int Gmax, int num_classes, float positive_overlap,
+    float negative_overlap, int* const* labels_out_host, float* const* locs_out_host,
+    float* const* targets_out_host, int capacity, int* counts_out, float* fg_bg_out,
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream, int class_specific_bbox) {
   ALArgs a;
+  if (class_specific_bbox != 0 && class_specific_bbox != 1) return SSAD_E_BADARG;
   const int rc = plan(&a, levels, A, k_min, field_sizes_host, N, Gmax);
   if (rc) return rc;
   if (!cell_anchors || !counts_out || !fg_bg_out || capacity < 0 || num_classes < 2 ||
@@ -325,6 +344,7 @@ int ssad_retinanet_anchor_labels(
   hipStream_t s = (hipStream_t)stream;
   a.cells = cell_anchors; a.gt_boxes = gt_boxes; a.gt_classes = gt_classes; a.gt_counts = gt_counts;
   a.pos_thr = positive_overlap; a.neg_thr = negative_overlap; a.num_classes = num_classes;
+  a.class_specific = class_specific_bbox;
   for (int l = 0; l < SSAD_MAX_LEVELS; ++l) {
     a.h[l] = l < levels ? crop_h_host[l] : 0;
     a.w[l] = l < levels ? crop_w_host[l] : 0;

@@ -149,7 +149,11 @@ struct WTile {
 };
 
 // See wino_conv_z_kernel (conv3x3_winograd.hip) for the skeleton and how it got there; what differs is marked F24.
-template <bool PAIRS>
+// ACCUM (SSAD_CONV_ACCUM_AUX, with SSAD_CONV_MASK_AUX): y = aux > 0 ? y + acc : 0, acc = what y held -- the data gradient
+// of the second of two convolutions that read one ReLU output (a shared RetinaNet tower: cls_pred's gradient has landed
+// in y unmasked, bbox_pred's is added here under the one mask).  Every lane reads exactly the elements it then writes.
+// An instantiation of its own: the kernels without it compile as before.
+template <bool PAIRS, bool ACCUM = false>
 __global__ __launch_bounds__(kBlock, 1) void wino24_conv_kernel(const WArgs args) {
   __shared__ float raw[NRAW * ZRAWP];
   __shared__ float vbuf[2 * VBUF];
@@ -481,6 +485,7 @@ __global__ __launch_bounds__(kBlock, 1) void wino24_conv_kernel(const WArgs args
       float bv[4];
       unsigned vos[4][2];
       f32x4 kvs[4][2];
+      f32x4 yvs[ACCUM ? 4 : 1][2];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = mt * 16 + kq * 4 + r;
@@ -491,6 +496,8 @@ __global__ __launch_bounds__(kBlock, 1) void wino24_conv_kernel(const WArgs args
           vos[r][a] = (whole && yy < H) ? (unsigned)((((long long)sn * M + m) * HW + yy * W + px) * 4) : kOOBOff;
           if (masked)
             kvs[r][a] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krsrc, vos[r][a], 0, 0));
+          if constexpr (ACCUM)
+            yvs[r][a] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(yrsrc, vos[r][a], 0, 0));
         }
       }
 #pragma unroll
@@ -523,7 +530,10 @@ __global__ __launch_bounds__(kBlock, 1) void wino24_conv_kernel(const WArgs args
             if (masked) {
               const f32x4 kv = kvs[r][a];
 #pragma unroll
-              for (int k = 0; k < 4; ++k) o[k] = kv[k] > 0.0f ? o[k] : 0.0f;
+              for (int k = 0; k < 4; ++k) {
+                if constexpr (ACCUM) o[k] = kv[k] > 0.0f ? o[k] + yvs[r][a][k] : 0.0f;
+                else o[k] = kv[k] > 0.0f ? o[k] : 0.0f;
+              }
             }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, o),
                                                    yrsrc, vo, 0, 0);
@@ -538,6 +548,7 @@ __global__ __launch_bounds__(kBlock, 1) void wino24_conv_kernel(const WArgs args
               if (px + k < W) {
                 float v = o[k];
                 if (sigm) v = 1.0f / (1.0f + expf(-v));
+                if constexpr (ACCUM) v += yout[px + k];
                 if (masked) v = L.aux[((long long)sn * M + m) * HW + yy * W + px + k] > 0.0f ? v : 0.0f;
                 yout[px + k] = v;
               }
@@ -597,6 +608,8 @@ int ssad_conv3x3_forward_wino24(const ssad_conv_level* lv, int n_levels, const f
                                 int Cout, int Cin, int flags, ssad_stream_t stream) {
   if (n_levels < 1 || n_levels > SSAD_MAX_CONV_PROBLEMS || Cout <= 0 || Cin <= 0) return SSAD_E_BADARG;
   if ((flags & SSAD_CONV_MASK_AUX) && (flags & SSAD_CONV_SIGMOID)) return SSAD_E_BADARG;
+  const bool accum = flags & SSAD_CONV_ACCUM_AUX;
+  if (accum && (!(flags & SSAD_CONV_MASK_AUX) || (flags & SSAD_CONV_RELU))) return SSAD_E_BADARG;
   for (int l = 0; l < n_levels; ++l) {
     if (!(lv[l].packed ? lv[l].packed : packed)) return SSAD_E_BADARG;
     if ((flags & SSAD_CONV_MASK_AUX) && !lv[l].aux) return SSAD_E_BADARG;
@@ -637,7 +650,10 @@ int ssad_conv3x3_forward_wino24(const ssad_conv_level* lv, int n_levels, const f
     long long grid = total < cus ? total : cus;
     if (grid * ZNT < total) grid = (total + ZNT - 1) / ZNT;
     a.xcd_group = 8;
-    if (use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+    if (accum) {
+      if (use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true, true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((wino24_conv_kernel<false, true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+    } else if (use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((wino24_conv_kernel<false>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;

@@ -36,7 +36,7 @@ constexpr int kT = 256;
 
 struct DArgs {
   const float* prob[SSAD_MAX_LEVELS];     // [1][A*C][H][W]
-  const float* delta[SSAD_MAX_LEVELS];    // [1][A*4][H][W]
+  const float* delta[SSAD_MAX_LEVELS];    // [1][A*4][H][W]; class_specific: [1][A*4*C][H][W]
   const double* cells;                    // [levels][A][4]
   int H[SSAD_MAX_LEVELS], W[SSAD_MAX_LEVELS];
   long long estart[SSAD_MAX_LEVELS + 1];  // first element of each level in the key array
@@ -44,6 +44,7 @@ struct DArgs {
   float th, th_last, nms_thresh, scale, xform_clip;
   int topn, dets_per_im, im_h, im_w;
   int n;                                  // levels * topn candidate slots
+  int class_specific;                     // RETINANET.CLASS_SPECIFIC_BBOX: channel a * 4 * C + 4 * cls + k
 };
 
 __device__ __forceinline__ int level_of(const DArgs& p, long long e) {
@@ -193,7 +194,10 @@ __global__ __launch_bounds__(kT) void det_decode_kernel(const DArgs p,
   const float bx = __fmul_rn((float)x, stride), by = __fmul_rn((float)y, stride);
   const float b0 = (float)((double)bx + c[0]), b1 = (float)((double)by + c[1]);
   const float b2 = (float)((double)bx + c[2]), b3 = (float)((double)by + c[3]);
-  const float* d = p.delta[l] + (long long)a * 4 * HW + (long long)y * W + x;
+  // class-agnostic: channels 4a .. 4a+3; class-specific: the box of (anchor, class), the layout the training loss
+  // addresses (retinanet.py:140-151)
+  const long long ch = p.class_specific ? (long long)a * 4 * p.C + 4 * cls : (long long)a * 4;
+  const float* d = p.delta[l] + ch * HW + (long long)y * W + x;
   const float dx = d[0], dy = d[HW], dw = fminf(d[2 * HW], p.xform_clip),
               dh = fminf(d[3 * HW], p.xform_clip);
   const float w = __fadd_rn(__fsub_rn(b2, b0), 1.0f), h = __fadd_rn(__fsub_rn(b3, b1), 1.0f);
@@ -424,13 +428,14 @@ int detect_body(
     const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
     float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
     int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
-    const ssad_detect_post* post) {
+    const ssad_detect_post* post, int class_specific) {
   Plan pl;
   DArgs a;
   const int rc = make_plan(levels, A, C, H_host, W_host, pre_nms_topn, &pl, a.estart);
   if (rc) return rc;
   if (!cls_prob_host || !box_pred_host || !cell_anchors || !dets_out || !count_out ||
-      dets_per_im < 1 || dets_per_im > pl.n || !(im_scale > 0.0f) || check_post(post))
+      dets_per_im < 1 || dets_per_im > pl.n || !(im_scale > 0.0f) || check_post(post) ||
+      (class_specific != 0 && class_specific != 1))
     return SSAD_E_BADARG;
   if (post_is_plain(post)) post = nullptr;
   const size_t need = ssad_retinanet_detect_ex_workspace_bytes(levels, A, C, H_host, W_host,
@@ -449,6 +454,7 @@ int detect_body(
   a.nms_thresh = nms_thresh; a.scale = im_scale; a.xform_clip = bbox_xform_clip;
   a.topn = pre_nms_topn; a.dets_per_im = dets_per_im; a.im_h = im_height; a.im_w = im_width;
   a.n = pl.n;
+  a.class_specific = class_specific;
   const size_t n = (size_t)pl.n;
   char* w = (char*)workspace;
   auto take = [&](size_t b) { char* r = w; w += al(b); return r; };
@@ -556,7 +562,7 @@ int ssad_retinanet_detect(
     int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream) {
   return detect_body(cls_prob_host, box_pred_host, cell_anchors, levels, A, C, k_min, H_host, W_host, inference_th,
                      pre_nms_topn, nms_thresh, dets_per_im, im_scale, im_height, im_width, bbox_xform_clip, dets_out,
-                     count_out, workspace, workspace_bytes, stream, nullptr);
+                     count_out, workspace, workspace_bytes, stream, nullptr, 0);
 }
 
 int ssad_retinanet_detect_ex(
@@ -568,7 +574,19 @@ int ssad_retinanet_detect_ex(
     const ssad_detect_post* post) {
   return detect_body(cls_prob_host, box_pred_host, cell_anchors, levels, A, C, k_min, H_host, W_host, inference_th,
                      pre_nms_topn, nms_thresh, dets_per_im, im_scale, im_height, im_width, bbox_xform_clip, dets_out,
-                     count_out, workspace, workspace_bytes, stream, post);
+                     count_out, workspace, workspace_bytes, stream, post, 0);
+}
+
+int ssad_retinanet_detect_class_specific(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, float nms_thresh, int dets_per_im,
+    float im_scale, int im_height, int im_width, float bbox_xform_clip, float* dets_out,
+    int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
+    const ssad_detect_post* post, int class_specific_bbox) {
+  return detect_body(cls_prob_host, box_pred_host, cell_anchors, levels, A, C, k_min, H_host, W_host, inference_th,
+                     pre_nms_topn, nms_thresh, dets_per_im, im_scale, im_height, im_width, bbox_xform_clip, dets_out,
+                     count_out, workspace, workspace_bytes, stream, post, class_specific_bbox);
 }
 
 }  // extern "C"

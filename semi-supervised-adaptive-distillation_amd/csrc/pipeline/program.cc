@@ -97,6 +97,7 @@ int run_op(const ssad_op& o, ssad_stream_t s) {
     case SSAD_OP_PACK_FILTER:
       return ssad_conv_pack_filter((const float*)p[0], i[0], i[1], (float*)p[1], (float*)p[2], s);
     case SSAD_OP_CONV3X3:
+      if ((i[3] & SSAD_CONV_ACCUM_AUX) && i[4] != 2) return SSAD_E_BADARG;      // the F(2x4) engine's epilogue only
       if (i[4] == 3)
         return ssad_conv3x3_forward_split((const ssad_conv_level*)p[0], i[0], (const float*)p[1], (const float*)p[2], i[1],
                                           i[2], i[3], (void*)p[3], (size_t)o.l[0], (const unsigned*)p[4], (unsigned*)p[5], s);

@@ -92,7 +92,7 @@ def subnet_engine(sw, who, name, cout, cin, which):
     if not sw.wino or (cout if fwd else cin) < 32:
         return Engine.DIRECT           # narrower than one 32-row tile of the Winograd engines
     pred = "_pred_" in name
-    if "bbox_pred" not in name and sw.split_conv & ((1 if fwd else 2) if pred else (4 if fwd else 8)):
+    if sw.split_conv & ((1 if fwd else 2) if pred else (4 if fwd else 8)) and _bbox_pred_on_split(name, cout, cin, fwd):
         return Engine.SPLIT
     if who == "teacher":
         f24 = fwd and cout >= 128 and sw.teacher_f24 >= (1 if pred else 2)
@@ -101,6 +101,18 @@ def subnet_engine(sw, who, name, cout, cin, which):
     else:
         f24 = cin >= 128 and sw.student_f24 & 1
     return Engine.F24 if f24 else Engine.F22
+
+
+def _bbox_pred_on_split(name, cout, cin, fwd):
+    """bbox_pred of the class-agnostic head (4 * A = 36 outputs) stays off the split-operand engine.  A class-specific
+    one (RETINANET.CLASS_SPECIFIC_BBOX: 4 * (num_classes - 1) * A outputs, 2880 at 81 classes, 11 tower layers' flops)
+    goes where cls_pred goes from 128 outputs -- the width from which the subnets' filter gradients take that engine
+    too (subnet_wgrad_split) -- provided the engine's pack-size function accepts the widths of this launch."""
+    if "bbox_pred" not in name:
+        return True
+    if cout < 128:
+        return False
+    return filter_floats(Engine.SPLIT)(*((cout, cin) if fwd else (cin, cout))) > 0
 
 
 def backbone_engine(sw, train, cout, cin):

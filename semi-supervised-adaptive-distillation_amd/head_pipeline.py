@@ -45,12 +45,20 @@ def cls_group(cfg):
     return cfg.num_classes if cfg.softmax else cfg.num_classes - 1
 
 
+def head_towers(cfg):
+    """The towers the subnets own: with RETINANET.SHARE_CLS_BBOX_TOWER there is no box tower and bbox_pred reads
+    the classification tower (retinanet_heads.py:164-171)."""
+    return ("cls",) if cfg.share_cls_bbox_tower else ("cls", "bbox")
+
+
 def head_param_specs(cfg):
     """(name, shape, is_bias, bucket) in the order the backward pass finishes
     them: prediction layers, then tower layers from the deepest to the first,
     cls and bbox subnet interleaved (their layers of equal depth run in the
     same launches).  Bucket "late" (ready first) = predictions + upper half of
-    the towers, bucket "early" = lower half."""
+    the towers, bucket "early" = lower half.  A shared tower (HeadConfig.share_cls_bbox_tower) has no
+    retnet_bbox_conv_* entries; a class-specific bbox_pred (HeadConfig.class_specific_bbox) has
+    4 * (num_classes - 1) * A outputs."""
     A, C, D = cfg.num_anchors, cls_group(cfg), cfg.fpn_dim
     specs = []
 
@@ -58,10 +66,10 @@ def head_param_specs(cfg):
         specs.append((stem + "_w", (cout, D, 3, 3), False, bucket))
         specs.append((stem + "_b", (cout,), True, bucket))
     add("retnet_cls_pred_fpn%d" % cfg.k_min, A * C, "late")
-    add("retnet_bbox_pred_fpn%d" % cfg.k_min, 4 * A, "late")
+    add("retnet_bbox_pred_fpn%d" % cfg.k_min, cfg.bbox_regr_dim * A, "late")
     for i in range(cfg.num_convs - 1, -1, -1):
         bucket = "late" if i >= cfg.num_convs // 2 else "early"
-        for tower in ("cls", "bbox"):
+        for tower in head_towers(cfg):
             add("retnet_%s_conv_n%d_fpn%d" % (tower, i, cfg.k_min), D, bucket)
     return specs
 
@@ -101,18 +109,25 @@ class DistillHeads(object):
     teacher, no PowSum / SigmoidAdaptiveDistillLoss, only SigmoidFocalLoss + SelectSmoothL1Loss.
     HeadConfig.softmax (RETINANET.SOFTMAX, distill=False only): cls_pred has A * num_classes rows, initialised with
     the builder's prior bias, and the loss segment is ONE SOFTMAX_FOCAL_FUSED record (SoftmaxFocalLoss and its
-    gradient in one pass over the logits) + SelectSmoothL1Loss; DESIGN 3.11a."""
+    gradient in one pass over the logits) + SelectSmoothL1Loss; DESIGN 3.11a.
+    HeadConfig.share_cls_bbox_tower (RETINANET.SHARE_CLS_BBOX_TOWER): no box tower in the student (nor in the teacher):
+    bbox_pred reads the last classification activation and that activation's gradient is the sum of both prediction
+    layers' data gradients under one ReLU mask.  HeadConfig.class_specific_bbox (RETINANET.CLASS_SPECIFIC_BBOX):
+    bbox_pred, its gradient and its filter are 4 * (num_classes - 1) * A wide; DESIGN 3.14."""
 
     F16 = False
 
     def __init__(self, cfg=None, N=2, shapes=synth.LEVEL_SHAPES_600, device="cuda",
                  student_init=None, teacher_init=None, teacher_bbox_tower=True,
                  lr=0.01, momentum=0.9, weight_decay=1e-4, process_group=None, world_size=1,
-                 distill=True, overlap_wgrad=None, blocked_io=False, teacher_fpn_dim=None):
+                 distill=True, overlap_wgrad=None, blocked_io=False, teacher_fpn_dim=None, shared_accumulate=None):
         """teacher_fpn_dim: FPN dimension of the TEACHER's subnets when it differs from cfg.fpn_dim (the student's):
         a thin student of RESNETS.CHANNEL_RATIO r has int(FPN.DIM * r) channels on every level while the teacher,
         built from its own cfg, keeps FPN.DIM.  The two networks' towers then have different (Cout, Cin) and run as
-        separate launches, each under the engine rules of its own width (fp32 pipeline only)."""
+        separate launches, each under the engine rules of its own width (fp32 pipeline only).
+        shared_accumulate (shared tower only; None: environment SSAD_SHARED_ACCUM, default on -- the same-call A/B is in
+        DESIGN 3.14): bbox_pred's data gradient adds itself to cls_pred's in its epilogue (CONV_ACCUM_AUX) where it runs
+        on the F(2x4) engine; off, or on any other engine: two unmasked data gradients, SUM_N and RELU_GRAD records."""
         self.cfg = cfg or HeadConfig()
         self.N, self.shapes, self.device = N, list(shapes), device
         self.distill = bool(distill)
@@ -124,6 +139,15 @@ class DistillHeads(object):
         if self.cfg.softmax and self.F16:
             raise K.KernelError("DistillHeadsF16: HeadConfig.softmax is not supported (there is no fp16 softmax "
                                 "head; the fp32 pipeline DistillHeads runs it)")
+        for switch in ("share_cls_bbox_tower", "class_specific_bbox"):
+            if getattr(self.cfg, switch) and self.F16:
+                raise K.KernelError("DistillHeadsF16: HeadConfig.%s is not supported (the fp16 subnets run two towers "
+                                    "and a 4 * A wide bbox_pred; the fp32 pipeline DistillHeads runs it)" % switch)
+        self.towers = head_towers(self.cfg)
+        self.box_tower = self.towers[-1]      # the tower bbox_pred reads
+        if shared_accumulate is None:
+            shared_accumulate = os.environ.get("SSAD_SHARED_ACCUM", "1") == "1"
+        self._shared_accumulate = bool(shared_accumulate) and self.cfg.share_cls_bbox_tower
         self.teacher_bbox_tower = teacher_bbox_tower and self.distill
         self.switches = Switches.read().for_subnets(self.distill, self.F16)     # the one read of the engine switches
         self.split_conv = self.switches.split_conv
@@ -182,25 +206,37 @@ class DistillHeads(object):
         self.labels = [torch.zeros((self.N, self.A, h, w), dtype=torch.int32, device=self.device)
                        for (h, w) in self.shapes]
         # student activations (kept for backward) and their gradients
-        self.act = {t: [lv(D) for _ in range(cfg.num_convs)] for t in ("cls", "bbox")}
-        self.cls_logits, self.bbox_pred = lv(self.A * self.C), lv(4 * self.A)
+        R = cfg.bbox_regr_dim * self.A
+        self.act = {t: [lv(D) for _ in range(cfg.num_convs)] for t in self.towers}
+        self.cls_logits, self.bbox_pred = lv(self.A * self.C), lv(R)
         self.d_cls_logits = lv(self.A * self.C)
-        self.d_bbox_pred = lv(4 * self.A)
+        self.d_bbox_pred = lv(R)
         # one gradient set per tower depth (not ping-pong): the filter gradient of a layer runs on an
         # auxiliary stream while the data-gradient chain continues, so its dY must stay intact
-        self.dbuf = {t: [lv(D) for _ in range(cfg.num_convs + 1)] for t in ("cls", "bbox")}
-        self.d_fpn = {t: lv(D) for t in ("cls", "bbox")}
+        self.dbuf = {t: [lv(D) for _ in range(cfg.num_convs + 1)] for t in self.towers}
+        self.d_fpn = {t: lv(D) for t in self.towers}
+        # shared tower: "accumulate" where bbox_pred's data gradient runs on the engine that has the epilogue, else "two_pass"
+        self.shared_form = None
+        if cfg.share_cls_bbox_tower:
+            accum = self._shared_accumulate and self.dgrad_engine[self._layers("bbox")[-1]] == Engine.F24
+            self.shared_form = "accumulate" if accum else "two_pass"
+        if self.shared_form == "two_pass":
+            # two-pass form: the two prediction layers' unmasked data gradients and their sum; the sum, masked, is
+            # dbuf["cls"][num_convs] (no operand of a launch aliases its output)
+            self.d_shared = {t: lv(D) for t in ("cls", "bbox", "sum")}
         if self.distill:
             # teacher scratch: two ping-pong feature sets per tower + probabilities
             Dt = self.Dt
-            self.t_buf = {"cls": [lv(Dt), lv(Dt)], "bbox": [lv(Dt), lv(Dt)]}
+            self.t_buf = {t: [lv(Dt), lv(Dt)] for t in self.towers}
             self.t_prob = lv(self.A * self.C)
-            self.t_bbox = lv(4 * self.A) if self.teacher_bbox_tower else None
+            self.t_bbox = lv(R) if self.teacher_bbox_tower else None
 
     # -- layer bookkeeping ----------------------------------------------------------
     def _layers(self, tower):
         cfg = self.cfg
         names = ["retnet_%s_conv_n%d_fpn%d" % (tower, i, cfg.k_min) for i in range(cfg.num_convs)]
+        if tower not in self.towers:      # shared tower: the box subnet is its prediction layer alone
+            names = []
         names.append("retnet_%s_pred_fpn%d" % (tower, cfg.k_min))
         return names
 
@@ -242,14 +278,18 @@ class DistillHeads(object):
              ("teacher_cls_pred", Engine.F22): 3, ("teacher_cls_pred", Engine.F24): 20,
              ("teacher_cls_pred", Engine.SPLIT): 25,
              ("bbox_pred", Engine.F22): 4, ("teacher_bbox_pred", Engine.F22): 4,
+             # a class-specific bbox_pred (>= 128 outputs) runs on cls_pred's engines
+             ("bbox_pred", Engine.F24): 30, ("teacher_bbox_pred", Engine.F24): 30,
+             ("bbox_pred", Engine.SPLIT): 31, ("teacher_bbox_pred", Engine.SPLIT): 31,
              ("pred_dgrad", Engine.F22): 16, ("pred_dgrad", Engine.F24): 24, ("pred_dgrad", Engine.SPLIT): 27,
              ("tower_dgrad", Engine.F22): 16, ("tower_dgrad", Engine.F24): 24, ("tower_dgrad", Engine.SPLIT): 29}
 
-    def _emit_conv(self, P, problems, Cout, Cin, flags, role, engine, teacher=False):
-        """One launch of independent convolutions of equal (Cout, Cin) on one engine; every output's |max| is folded."""
+    def _emit_conv(self, P, problems, Cout, Cin, flags, role, engine, teacher=False, fold=True):
+        """One launch of independent convolutions of equal (Cout, Cin) on one engine; every output's |max| is folded
+        (fold=False: the output is not final -- a later launch accumulates into it -- so no word is kept for it)."""
         klass = 18 if engine == Engine.DIRECT else self.KLASS[("teacher_" if teacher else "") + role, engine]
         return emit_conv3x3(P, klass, self._rows(problems), Cout, Cin, flags, engine, self._amax, self._split,
-                            levels=len(self.shapes), own_table=True)
+                            levels=len(self.shapes), own_table=True, fold=fold)
 
     def _emit_group(self, P, probs, role, flags, bind=False):
         """probs: [(who, layer, problem)], forward convolutions that may share launches: one launch per (Cout, Cin,
@@ -271,7 +311,7 @@ class DistillHeads(object):
 
     def _emit_wgrad(self, P, xs, dys, name, Cout, klass):
         exact = 19 if self.fwd_engine["student", name] == Engine.DIRECT else klass
-        return emit_conv3x3_wgrad(P, (exact, {5: 68, 6: 69}.get(klass, klass)), xs, dys, self.grads[name + "_w"],
+        return emit_conv3x3_wgrad(P, (exact, {5: 68, 6: 69, 7: 40}.get(klass, klass)), xs, dys, self.grads[name + "_w"],
                                   self.grads[name + "_b"], Cout, self.D, subnet_wgrad_split(self.switches, Cout, self.D),
                                   self._amax, self._fork, own_table=True)
 
@@ -354,11 +394,11 @@ class DistillHeads(object):
         the 256 CUs to 99 % where five separate launches would each leave a partial last wave.
         Teacher cls_pred carries the Sigmoid epilogue (retinanet_heads.py:153-163)."""
         cfg = self.cfg
-        tx = {"cls": self.t_fpn_in, "bbox": self.t_fpn_in}
-        sx = {"cls": self.fpn_in, "bbox": self.fpn_in}
+        tx = {t: self.t_fpn_in for t in self.towers}
+        sx = {t: self.fpn_in for t in self.towers}
         for i in range(cfg.num_convs):
             probs = []
-            for t in ("cls", "bbox"):
+            for t in self.towers:
                 name = self._layers(t)[i]
                 if self.distill and (t == "cls" or self.teacher_bbox_tower):
                     out = self.t_buf[t][i & 1]
@@ -375,9 +415,10 @@ class DistillHeads(object):
                              "cls_pred", K.CONV_SIGMOID)
         self._emit_group(P, [("student", cp, (sx["cls"], self.cls_logits, None, self.packed[cp][0], self.params[cp + "_b"]))],
                          "cls_pred", 0)
-        probs = [("student", bp, (sx["bbox"], self.bbox_pred, None, self.packed[bp][0], self.params[bp + "_b"]))]
+        bt = self.box_tower
+        probs = [("student", bp, (sx[bt], self.bbox_pred, None, self.packed[bp][0], self.params[bp + "_b"]))]
         if self.teacher_bbox_tower:
-            probs.append(("teacher", bp, (tx["bbox"], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"])))
+            probs.append(("teacher", bp, (tx[bt], self.t_bbox, None, self.t_packed_for(bp), self.teacher[bp + "_b"])))
         self._emit_group(P, probs, "bbox_pred", 0)
 
     def t_packed_for(self, name):
@@ -487,19 +528,48 @@ class DistillHeads(object):
         bucket is complete (mark "backward_late_done"): its all-reduce is issued there."""
         cfg, D = self.cfg, self.D
         nl = cfg.num_convs
+        shared = cfg.share_cls_bbox_tower
+        # shared tower, accumulate form: cls_pred's data gradient lands unmasked in the tower's gradient buffer and bbox_pred's
+        # adds itself under the one ReLU mask in its own epilogue -- where bbox_pred's data gradient is on the F(2x4)
+        # engine, the one engine with that epilogue (subnet_engine: the class-agnostic 36-wide layer by default)
         dy = {"cls": self.d_cls_logits, "bbox": self.d_bbox_pred}
         for t, klass_w in (("cls", 6), ("bbox", 7)):
             name = self._layers(t)[-1]
-            x_in = self.act[t][nl - 1]
+            x_in = self.act[t if t in self.towers else self.box_tower][nl - 1]
             Cout = self.params[name + "_b"].numel()
             self._emit_wgrad(P, x_in, dy[t], name, Cout, klass_w)
-            out = self.dbuf[t][nl]
-            self._emit_conv(P, [(dy[t], out, x_in, self.packed[name][1], None)], D, Cout, K.CONV_MASK_AUX,
-                            "pred_dgrad", self.dgrad_engine[name])
+            engine = self.dgrad_engine[name]
+            if self.shared_form == "accumulate":
+                out = self.dbuf["cls"][nl]
+                if t == "cls":
+                    self._emit_conv(P, [(dy[t], out, None, self.packed[name][1], None)], D, Cout, 0, "pred_dgrad", engine,
+                                    fold=False)
+                else:
+                    self._emit_conv(P, [(dy[t], out, x_in, self.packed[name][1], None)], D, Cout,
+                                    K.CONV_MASK_AUX | K.CONV_ACCUM_AUX, "pred_dgrad", engine)
+            elif shared:
+                # both data gradients land unmasked in buffers of their own and are summed below
+                out = self.d_shared[t]
+                self._emit_conv(P, [(dy[t], out, None, self.packed[name][1], None)], D, Cout, 0, "pred_dgrad", engine,
+                                fold=False)
+            else:
+                out = self.dbuf[t][nl]
+                self._emit_conv(P, [(dy[t], out, x_in, self.packed[name][1], None)], D, Cout, K.CONV_MASK_AUX,
+                                "pred_dgrad", engine)
             dy[t] = out
+        if self.shared_form == "two_pass":
+            # d(last tower activation) = ReluGradient(cls_pred's + bbox_pred's data gradient): the reference's gradient
+            # Sum of a blob read by two convolutions, then the tower's ReluGradient (one mask for the sum)
+            x_in, out = self.act["cls"][nl - 1], self.dbuf["cls"][nl]
+            for a, b, s_, d, x in zip(dy["cls"], dy["bbox"], self.d_shared["sum"], out, x_in):
+                ptrs = (C.c_void_p * 2)(a.data_ptr(), b.data_ptr())
+                P.add(PR.SUM_N, 39, i=(2,), l=(d.numel(),), p=(ptrs, s_), work=12.0 * d.numel(), keep=[a, b, s_])
+                P.add(PR.RELU_GRAD, 39, p=(x, s_, d), l=(d.numel(),), work=12.0 * d.numel(), keep=[x, s_, d])
+        if shared:
+            dy = {"cls": self.dbuf["cls"][nl]}
         for li in range(nl - 1, -1, -1):
             probs = []
-            for t in ("cls", "bbox"):
+            for t in self.towers:
                 name = self._layers(t)[li]
                 x_in = self.act[t][li - 1] if li > 0 else self.fpn_in
                 _, arr = self._emit_wgrad(P, x_in, dy[t], name, D, 5)
@@ -510,7 +580,7 @@ class DistillHeads(object):
                 probs.append((dy[t], out, x_in if li > 0 else None, self.packed[name][1], None))
                 dy[t] = out
             self._emit_conv(P, probs, D, D, K.CONV_MASK_AUX if li > 0 else 0, "tower_dgrad",
-                            same_engine(self.dgrad_engine[self._layers(t)[li]] for t in ("cls", "bbox")))
+                            same_engine(self.dgrad_engine[self._layers(t)[li]] for t in self.towers))
             if li == nl // 2:
                 P.mark("backward_late_done")
         if "backward_late_done" not in P.marks:

@@ -19,6 +19,7 @@ CONV_RELU = 1
 CONV_MASK_AUX = 2
 CONV_SIGMOID = 4
 CONV_SPLIT_TAIL = 8
+CONV_ACCUM_AUX = 32    # F(2x4) engine, with CONV_MASK_AUX: y = aux > 0 ? y + acc : 0 (acc = y before the launch)
 
 
 class KernelError(RuntimeError):
@@ -938,9 +939,12 @@ def conv3x3_split_items(shapes, Cout):
     return n
 
 
-def conv3x3_forward_wino24(xs, packed, bias, Cout, *, relu=False, sigmoid=False, out=None, mask_by=None):
+def conv3x3_forward_wino24(xs, packed, bias, Cout, *, relu=False, sigmoid=False, out=None, mask_by=None, accumulate=False):
     """conv3x3_forward on the F(2x4, 3x3) engine (xs: levels sharing the filter).  mask_by: the data-gradient form --
-    y = mask > 0 ? y : 0 (fused ReluGradient), packed = the data-gradient pack, Cout = the layer's input channels."""
+    y = mask > 0 ? y : 0 (fused ReluGradient), packed = the data-gradient pack, Cout = the layer's input channels.
+    accumulate (with mask_by and out): y = mask > 0 ? y + out : 0, out read before it is overwritten."""
+    if accumulate and (mask_by is None or out is None):
+        raise KernelError("conv3x3_forward_wino24: accumulate=True needs mask_by= and out=")
     L = lib()
     for x in xs:
         _f32c(x, "conv input")
@@ -948,6 +952,7 @@ def conv3x3_forward_wino24(xs, packed, bias, Cout, *, relu=False, sigmoid=False,
     ys = out if out is not None else [
         torch.empty((x.shape[0], Cout, x.shape[2], x.shape[3]), dtype=torch.float32, device="cuda") for x in xs]
     flags = (CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0) | (CONV_MASK_AUX if mask_by is not None else 0)
+    flags |= CONV_ACCUM_AUX if accumulate else 0
     arr = _conv_levels(xs, ys, mask_by)
     _check(L.ssad_conv3x3_forward_wino24(arr, len(xs), _ptr(packed), _ptr(bias), Cout, Cin, flags, _stream()),
            "conv3x3_forward_wino24")

@@ -18,6 +18,7 @@ class AnchorConfig(object):
     coarsest_stride = 128                # FPN.COARSEST_STRIDE
     train_max_size = 1000                # TRAIN.MAX_SIZE
     num_classes = 81                     # MODEL.NUM_CLASSES
+    class_specific_bbox = False          # RETINANET.CLASS_SPECIFIC_BBOX
 
 
 def _whctrs(a):

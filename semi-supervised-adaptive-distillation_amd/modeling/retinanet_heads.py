@@ -45,6 +45,8 @@ class HeadConfig:
     use_cudnn_engine: bool = True         # the reference asks for engine=CUDNN
     fuse_relu: bool = False               # extension: fold Relu into the conv
     softmax: bool = False                 # RETINANET.SOFTMAX: softmax head over num_classes (background kept)
+    share_cls_bbox_tower: bool = False    # RETINANET.SHARE_CLS_BBOX_TOWER: bbox_pred reads the cls tower, no box tower
+    class_specific_bbox: bool = False     # RETINANET.CLASS_SPECIFIC_BBOX: one box per foreground class and anchor
 
     @classmethod
     def for_body(cls, body_cfg, **kw):
@@ -55,6 +57,11 @@ class HeadConfig:
     @property
     def num_anchors(self):
         return len(self.aspect_ratios) * self.scales_per_octave
+
+    @property
+    def bbox_regr_dim(self):
+        """Box-regression channels per anchor (retinanet_heads.py:83-85)."""
+        return 4 * (self.num_classes - 1) if self.class_specific_bbox else 4
 
     @property
     def loss_scale(self):
@@ -141,14 +148,19 @@ def add_fpn_retinanet_outputs(model, blobs_in, dim_in=None, prefix=""):
     towers = (
         # (tower name, prediction blob stem, prediction width, prediction bias init)
         ("cls", "retnet_cls_pred", cls_pred_dim * A, retinanet_bias_init(cfg)),
-        ("bbox", "retnet_bbox_pred", 4 * A, ZERO),
+        ("bbox", "retnet_bbox_pred", cfg.bbox_regr_dim * A, ZERO),
     )
     feats = {}
     preds = {lvl: [None, None] for lvl in cfg.levels()}
     # The reference builds the whole cls subnet (towers + logits [+ teacher
-    # sigmoid]) first, then the bbox towers, then the bbox predictions.
+    # sigmoid]) first, then the bbox towers, then the bbox predictions.  With a
+    # shared tower there are no bbox towers: bbox_pred reads the cls tower's
+    # last blob (retinanet_heads.py:164-171).
     for ti, (tower, pred_stem, pred_dim, pred_bias) in enumerate(towers):
         for lvl in cfg.levels():
+            if tower == "bbox" and cfg.share_cls_bbox_tower:
+                feats[(tower, lvl)] = feats[("cls", lvl)]
+                continue
             x = blobs_in[cfg.k_max - lvl]
             for i in range(cfg.num_convs):
                 stem = prefix + "retnet_%s_conv_n%d_fpn" % (tower, i)

@@ -75,6 +75,15 @@ KLASS = {
     29: dict(name="subnet tower data gradient, split-operand engine (conv3x3_split_kernel + its split pass; |max| words from the table, class 73)",
              bound="mfma16", wino=True, exec_div=1.0 / 3.0),
     24: dict(name="subnet conv3x3 data gradient, F(2x4,3x3) (wino24_conv_kernel)", bound="mfma", wino=True, exec_div=3.0),
+    # a class-specific bbox_pred (RETINANET.CLASS_SPECIFIC_BBOX, 4 * (num_classes - 1) * A outputs) on cls_pred's engines
+    30: dict(name="class-specific bbox_pred conv3x3 fwd, F(2x4,3x3) (wino24_conv_kernel)", bound="mfma", wino=True, exec_div=3.0),
+    31: dict(name="class-specific bbox_pred conv3x3 fwd, split-operand engine (conv3x3_split_kernel + its split pass; |max| words from the table, class 73)",
+             bound="mfma16", wino=True, exec_div=1.0 / 3.0),
+    40: dict(name="class-specific bbox_pred filter gradient, split-operand engine (wsplit_kernel + reduce + bias grad)",
+             bound="mfma16", wino=True, exec_div=1.0 / 3.0),
+    # a shared tower (RETINANET.SHARE_CLS_BBOX_TOWER): cls_pred's + bbox_pred's data gradients summed, then the tower's ReluGradient
+    39: dict(name="shared tower: Sum of the two prediction layers' data gradients + ReluGradient (sum_n_kernel, relu_grad_kernel per level)",
+             bound="hbm"),
     # direct (non-Winograd) engine
     18: dict(name="subnet conv3x3 fwd/dgrad, direct engine (conv3x3_kernel)", bound="mfma", wino=False),
     19: dict(name="subnet conv3x3 filter gradient, direct engine (conv3x3_wgrad_kernel + reduce)",

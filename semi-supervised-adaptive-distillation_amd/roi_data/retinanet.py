@@ -16,11 +16,20 @@ class RetinanetLabeler(object):
     gt_classes int32  [N][Gmax] device, gt_counts int32 [N] device
     Returns a dict with the reference's blob names (labels / locs / targets per
     level, `retnet_fg_num`, `retnet_bg_num`); the list tensors are views of
-    length M (one host sync to read the five counts)."""
+    length M (one host sync to read the five counts).
+
+    class_specific_bbox (None: cfg.class_specific_bbox; RETINANET.CLASS_SPECIFIC_BBOX): column 1 of
+    `retnet_roi_fg_bbox_locs_fpn{l}` is 4 * (label - 1) + 4 * (num_classes - 1) * anchor instead of
+    4 * anchor (retinanet.py:140-151,288-293)."""
 
     def __init__(self, N, Gmax, im_height, im_width, cfg=AnchorConfig, capacity=1 << 16,
-                 device="cuda"):
+                 device="cuda", class_specific_bbox=None):
         self.cfg, self.N, self.Gmax, self.capacity = cfg, N, Gmax, capacity
+        if class_specific_bbox is None:
+            class_specific_bbox = getattr(cfg, "class_specific_bbox", False)
+        if not isinstance(class_specific_bbox, (bool, np.bool_)):
+            raise K.KernelError("class_specific_bbox= is a boolean")
+        self.class_specific_bbox = bool(class_specific_bbox)
         self.levels = cfg.k_max - cfg.k_min + 1
         self.A = cfg.scales_per_octave * len(cfg.aspect_ratios)
         self.fs = field_sizes(cfg)
@@ -54,7 +63,7 @@ class RetinanetLabeler(object):
                 raise K.KernelError("ground truth must be contiguous device tensors (f32, i32, i32)")
         if tuple(gt_boxes.shape) != (self.N, self.Gmax, 4):
             raise K.KernelError("gt_boxes must be N x Gmax x 4")
-        rc = K.lib().ssad_retinanet_anchor_labels(
+        args = (
             C.c_void_p(self.cells.data_ptr()), self.levels, self.A, cfg.k_min, self._fs, self._h,
             self._w, C.c_void_p(gt_boxes.data_ptr()), C.c_void_p(gt_classes.data_ptr()),
             C.c_void_p(gt_counts.data_ptr()), self.N, self.Gmax, cfg.num_classes,
@@ -62,6 +71,10 @@ class RetinanetLabeler(object):
             self._locs, self._targets, self.capacity, C.c_void_p(self.counts.data_ptr()),
             C.c_void_p(self.fg_bg.data_ptr()), C.c_void_p(self.ws.data_ptr()),
             C.c_size_t(self.ws.numel()), K._stream())
+        if self.class_specific_bbox:
+            rc = K.lib().ssad_retinanet_anchor_labels_ex(*args, 1)
+        else:
+            rc = K.lib().ssad_retinanet_anchor_labels(*args)
         if rc:
             raise K.KernelError("retinanet_anchor_labels failed (%d)" % rc)
         counts = self.counts.cpu().numpy()
@@ -95,12 +108,22 @@ class RetinanetDetector(object):
     the top-k): `__call__` then takes either the foreground probabilities [1][A*C][H][W] as above, or, with
     `from_logits=True`, the raw cls_pred logits [1][A*(C+1)][H][W] (background first in every anchor's group),
     which it turns into the former with kernels.group_spatial_softmax(drop_background=True) in buffers
-    allocated here."""
+    allocated here.
+
+    `class_specific_bbox=True` is the RETINANET.CLASS_SPECIFIC_BBOX head: box deltas are [1][A*4*C][H][W] and a
+    candidate (anchor a, class c, y, x) takes its four deltas from channels a*4*C + 4*c + k, the layout the
+    training loss addresses (RetinanetLabeler(class_specific_bbox=True)).  The reference's own test path cannot
+    run such a head (test_retinanet.py:120-121 reshapes box_pred to (N, A, 4, H, W)); DESIGN.md lists this
+    as UNPINNED."""
 
     def __init__(self, level_shapes, cfg=AnchorConfig, inference_th=0.05, pre_nms_topn=1000,
-                 nms_thresh=0.5, dets_per_im=100, device="cuda", *, soft_nms=None, bbox_vote=None, softmax=False):
+                 nms_thresh=0.5, dets_per_im=100, device="cuda", *, soft_nms=None, bbox_vote=None, softmax=False,
+                 class_specific_bbox=False):
         self.post = self._post(soft_nms, bbox_vote)
         self.softmax = self._softmax_args(softmax, False)
+        if not isinstance(class_specific_bbox, (bool, np.bool_)):
+            raise K.KernelError("class_specific_bbox= is a boolean")
+        self.class_specific_bbox = bool(class_specific_bbox)
         self.cfg = cfg
         self.levels = len(level_shapes)
         self.A = cfg.scales_per_octave * len(cfg.aspect_ratios)
@@ -182,10 +205,12 @@ class RetinanetDetector(object):
             if tuple(t.shape) != (1, self.A * self.C, h, w) or t.dtype != torch.float32 or \
                     not t.is_contiguous() or not t.is_cuda:
                 raise K.KernelError("cls_prob must be 1 x A*C x H x W contiguous float32 device tensors")
+        box_ch = self.A * 4 * (self.C if self.class_specific_bbox else 1)
         for t, (h, w) in zip(box_preds, self.shapes):
-            if tuple(t.shape) != (1, self.A * 4, h, w) or t.dtype != torch.float32 or \
+            if tuple(t.shape) != (1, box_ch, h, w) or t.dtype != torch.float32 or \
                     not t.is_contiguous() or not t.is_cuda:
-                raise K.KernelError("box_pred must be 1 x A*4 x H x W contiguous float32 device tensors")
+                raise K.KernelError("box_pred must be 1 x %s x H x W contiguous float32 device tensors"
+                                    % ("A*4*C" if self.class_specific_bbox else "A*4"))
         PtrArr = C.c_void_p * self.levels
         args = (
             PtrArr(*[t.data_ptr() for t in cls_probs]), PtrArr(*[t.data_ptr() for t in box_preds]),
@@ -195,7 +220,10 @@ class RetinanetDetector(object):
             C.c_float(float(np.log(1000. / 16.))), C.c_void_p(self.out.data_ptr()),
             C.c_void_p(self.count.data_ptr()), C.c_void_p(self.ws.data_ptr()),
             C.c_size_t(self.ws.numel()), K._stream())
-        if self.post is None:
+        if self.class_specific_bbox:
+            rc = K.lib().ssad_retinanet_detect_class_specific(
+                *args, C.byref(self.post) if self.post is not None else C.c_void_p(0), 1)
+        elif self.post is None:
             rc = K.lib().ssad_retinanet_detect(*args)
         else:
             rc = K.lib().ssad_retinanet_detect_ex(*args, C.byref(self.post))

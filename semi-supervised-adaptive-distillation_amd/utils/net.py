@@ -98,6 +98,24 @@ def initialize_from_weights_file(store, weights_file, teacher_weights_file=None,
     return _initialize_heads(store, src, teacher_weights_file is not None, softmax=softmax)
 
 
+class BboxPredWidthError(ValueError):
+    """A weights file whose bbox_pred has another number of outputs than the head it is loaded into: a
+    RETINANET.CLASS_SPECIFIC_BBOX file (4 * (num_classes - 1) * A outputs) into a class-agnostic head (4 * A) or the
+    other way round.  Names the blob and both shapes."""
+
+
+def _check_bbox_pred_width(dst, name, arr):
+    """The reference reports and skips any mismatching blob (net.py:106-119); a box regressor of the other layout
+    skipped in silence leaves a randomly initialised bbox_pred under trained towers, so this one is refused."""
+    if "retnet_bbox_pred_" not in name:
+        return
+    have, want = tuple(np.asarray(arr).shape), tuple(dst[name.split("/")[-1]].shape)
+    if have[:1] != want[:1]:
+        raise BboxPredWidthError(
+            "%s has shape %s in the weights file, the head was built for %s (HeadConfig.class_specific_bbox decides "
+            "the width: 4 * (num_classes - 1) * A outputs when set, 4 * A otherwise)" % (name, have, want))
+
+
 def _softmax_store(store):
     return bool(getattr(getattr(store, "cfg", None), "softmax", False))
 
@@ -109,6 +127,11 @@ def _initialize_heads(store, src, teacher_file_given=False, softmax=False):
         raise ValueError("softmax=True: the parameter store was not built for a softmax head "
                          "(HeadParamStore(HeadConfig(softmax=True)))")
     refuse_cls_pred = _softmax_store(store) and not softmax
+    # (before anything is fed: a refused file leaves the store as it was)
+    for params, prefix in ((store.params, ""), (store.teacher, "teacher/")):
+        for name, _, _, _ in params.specs if params is not None else ():
+            if prefix + name in src:
+                _check_bbox_pred_width(params, prefix + name, src[prefix + name])
     for name, _, _, _ in store.params.specs:
         if name not in src:
             logger.info("%s not found", name)
