@@ -687,8 +687,10 @@ SSAD_API int ssad_subsample_grad(const float* dy, int N, int C, int H, int W, in
 /* Grouped 3x3 convolution, pad 1, stride 1 or 2, forward (ResNeXt's cardinality-64 layer:
  * detectron/lib/modeling/ResNet.py:247-258; conv_op_impl.h:93-98,126-173), NCHW fp32:
  * x [N][C][H][W], filter [C][C/group][3][3] packed once into MFMA operand order, bias [C] or NULL
- * -> y [N][C][OH][OW], OH = (H-1)/stride + 1.  Channels per group 4, 8, 16 or 32
- * (SSAD_E_BADARG / -1 otherwise: use the default engine). */
+ * -> y [N][C][OH][OW], OH = (H-1)/stride + 1.  Channels per group 4, 8, 16, 32 (X-101-64x4d's
+ * res2..res5) or 64 (X-101-32x8d's res5; a kernel of its own that stages the input in channel
+ * chunks: same numerics class, another summation order); SSAD_E_BADARG / -1 otherwise: use the
+ * default engine.  ssad_grouped_conv3x3_filter_floats = group * max(cg / 16, 1) * (9 cg / 4) * 64. */
 SSAD_API long long ssad_grouped_conv3x3_filter_floats(int C, int group);
 SSAD_API int ssad_grouped_conv3x3_pack_filter(const float* w, int C, int group, float* packed,
                                               ssad_stream_t stream);

@@ -49,10 +49,20 @@ from .modeling.resnet_fpn import ChannelRatioError, channel_widths
 # pixels (all images) a pointwise launch needs before the split-operand GEMM pays (see NativeResNetFPN._gemm)
 GEMM_SPLIT_MIN_PIXELS = 8192
 
-ARCHS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3)}
+ARCHS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3), "x101-32x8d": (3, 4, 23, 3)}
 # ResNeXt (ResNet.py:247-258): name -> (groups, width per group); the stride sits on the 3x3
-# (RESNETS.STRIDE_1X1 = False).  Forward only: it is the frozen teacher of BASELINE config 5.
-GROUPED = {"x101-64x4d": (64, 4)}
+# (RESNETS.STRIDE_1X1 = False).  Forward only: the frozen teachers of BASELINE config 5 (64x4d) and of the
+# reference's retinanet_X-101-32x8d-FPN configurations (groups 8, 16, 32 and 64 channels wide at res2..res5).
+GROUPED = {"x101-64x4d": (64, 4), "x101-32x8d": (32, 8)}
+
+
+def check_f16_grouped(arch):
+    """The fp16-storage backbone's grouped 3x3 (grouped_f16.hip) serves groups of up to 32 channels; a ResNeXt whose
+    res5 groups (8 x width per group) are wider is an fp32 network only.  Raises KernelError; touches no device."""
+    if arch in GROUPED and 8 * GROUPED[arch][1] > 32:
+        raise K.KernelError("native backbone: %s has no fp16-storage backbone: the fp16 grouped kernel stops at "
+                            "32-wide groups and its res5 groups are %d wide; use the fp32 backbone"
+                            % (arch, 8 * GROUPED[arch][1]))
 
 
 def student_widths(arch, channel_ratio, fpn_dim=256):
@@ -101,6 +111,8 @@ class NativeResNetFPN(object):
                                 "(backbone_f16's kernels were written for the full widths); use the fp32 backbone"
                                 % (channel_ratio,))
         self.widths = student_widths(arch, channel_ratio, fpn_dim)       # (before anything touches the library)
+        if getattr(self, "F16", False):
+            check_f16_grouped(arch)
         self.channel_ratio = float(channel_ratio)
         if arch in GROUPED and train:
             raise K.KernelError("native backbone: %s is forward only (the frozen teacher); its grouped 3x3 has no "
@@ -924,6 +936,9 @@ class NativeDistillModel(object):
             raise K.KernelError("NativeDistillModel: student_channel_ratio %r with the fp16-storage backbones is not "
                                 "supported (backbone_f16's kernels were written for the full widths)"
                                 % (student_channel_ratio,))
+        if self.backbone_f16:
+            for arch in (student_arch, teacher_arch if self.has_teacher else None):
+                check_f16_grouped(arch)
         want_s = student_widths(student_arch, student_channel_ratio).fpn_dim      # (raises before any allocation)
         if getattr(heads, "D", want_s) != want_s:
             raise K.KernelError("NativeDistillModel: the subnets were built for FPN dimension %d, a %s student of "

@@ -22,7 +22,7 @@
 //    neighbouring groups (4 at cg = 4, 2 at cg = 8, else 1): narrow groups would otherwise give a
 //    workgroup too little to do (measured 0.77 -> see DESIGN.md 3.6 for res2's layer).
 // Groups narrower than 16 channels leave MFMA rows idle (res2: cg = 4, res3: cg = 8 -- seven small
-// layers); cg = 32 uses two row tiles.
+// layers); cg = 32 uses two row tiles.  cg = 64 (X-101-32x8d's res5) has a kernel of its own, further down.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -153,6 +153,159 @@ int launch(GArgs a, int stride, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// ---- groups of 64 channels (ResNeXt-101-32x8d's res5: 2048 channels in 32 groups) ----
+// The design above does not stretch to cg = 64: MT * 9cg/4 = 576 filter registers per wave, and a stride-2 halo
+// of all 64 channels is 148 KB.  Here one workgroup is one group's 8 x 16 output tile and each of the four waves
+// owns ONE 16-row tile of the group's 64 output channels and walks all eight pixel rows:
+//  * the input is staged in chunks of 16 channels at stride 1 (13 KB) and of 8 at stride 2 (8 x 17 x 33 floats =
+//    18 KB) and the reduction runs chunk-major, k = (chunk, tap, channel in chunk); the eight rows' accumulators
+//    (32 registers) live across the chunks.  The sum order therefore differs from the narrower widths' (fp32
+//    round-off only);
+//  * the chunk loop is software-pipelined through registers: a thread stages the same one (stride 1) or three
+//    (stride 2) halo positions of every channel of a chunk, fetches the NEXT chunk's floats and its A operands
+//    (coalesced, from the same packed order as above, s = tap * 16 + c / 4) before the current chunk's MFMAs and
+//    writes them to the one LDS buffer after them.  Eight channels at stride 2 because 3 x 16 staged floats, their
+//    addresses and two sets of 36 A operands do not fit 256 registers at two workgroups per CU;
+//  * two pixel rows share each A operand: two independent accumulator chains, so the 40-cycle dependent latency
+//    of 16x16x4 never stalls its 32-cycle issue (a single chain, as in the cg <= 16 path, loses a fifth);
+//  * ds_read_b32 banks are (address / 4) % 32 within a 32-lane half, i.e. lanes (j, kk) and (j, kk + 1): at
+//    stride 1 the 16 columns take 16 consecutive banks, so PLANE % 32 == 16 puts kk + 1 on the other 16; at
+//    stride 2 they take the even banks, so an odd PLANE puts kk + 1 on the odd ones.  Both are conflict-free.
+template <int S>
+struct Geo64 {
+  static constexpr int CK = S == 1 ? 16 : 8, NCK = 64 / CK, KC = 9 * CK / 4;      // chunk channels, chunks, steps per chunk
+  static constexpr int IR = (TR - 1) * S + 3, IC = (TC - 1) * S + 3, CP = IC;
+  static constexpr int PLANE = S == 1 ? (IR * CP + 15) / 32 * 32 + 16 : ((IR * CP) | 1);
+  static_assert(PLANE >= IR * CP && PLANE % 32 != 0, "plane pitch");
+  static_assert(CK * PLANE * 4 <= 64 * 1024, "static LDS");
+};
+
+template <int S>
+__global__ __launch_bounds__(kThreads, 2) void grouped_conv3x3_cg64_kernel(const GArgs a) {
+  typedef Geo64<S> Q;
+  constexpr int CG = 64, CK = Q::CK, KC = Q::KC, IR = Q::IR, IC = Q::IC, CP = Q::CP, PLANE = Q::PLANE;
+  __shared__ float tile[CK * PLANE];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;      // wave = the group's 16-row tile
+  const int j = lane & 15, kk = lane >> 4;
+  int b = blockIdx.x;
+  const int tx = b % a.tiles_x; b /= a.tiles_x;
+  const int ty = b % a.tiles_y; b /= a.tiles_y;
+  const int g = b % a.G, n = b / a.G;
+  const int oy0 = ty * TR, ox0 = tx * TC;
+  const int iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
+
+  const float* wp = a.wp + ((long long)g * 4 + wave) * (9 * CG / 4) * 64 + lane;
+  const float* xg = a.x + ((long long)n * a.C + (long long)g * CG) * a.H * a.W;
+  const float* base = tile + kk * PLANE + j * S;
+
+  f32x4 acc[TR / 2][2];
+#pragma unroll
+  for (int rp = 0; rp < TR / 2; ++rp) acc[rp][0] = acc[rp][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // Software pipeline over the chunks: the next chunk's input (SLOTS x CK floats per thread) and A operands are
+  // fetched into registers BEFORE the current chunk's MFMAs and written to the one LDS buffer after them, so their
+  // latency hides behind the arithmetic of the same workgroup.
+  // A thread stages the same SLOTS halo positions of every channel of a chunk: their addresses and bounds are
+  // worked out once, a channel is a uniform step of H * W, and the LDS offset of (channel, position) is immediate.
+  constexpr int NPOS = IR * IC, SLOTS = (NPOS + kThreads - 1) / kThreads;
+  float pre[SLOTS][CK], wr[KC];
+  long long goff[SLOTS];
+  int loff[SLOTS];
+  bool inside[SLOTS];
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) {
+    const int pos = tid + k * kThreads, r = pos / IC, p = pos % IC;
+    const int iy = iy0 + r, ix = ix0 + p;
+    inside[k] = pos < NPOS && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+    goff[k] = (long long)iy * a.W + ix;
+    loff[k] = pos < NPOS ? r * CP + p : -1;
+  }
+  const long long HW = (long long)a.H * a.W;
+  auto fetch = [&](int q) {
+    const float* xq = xg + (long long)q * CK * HW;
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k)
+#pragma unroll
+      for (int c = 0; c < CK; ++c) pre[k][c] = inside[k] ? xq[c * HW + goff[k]] : 0.0f;    // zero outside the image
+  };
+  // the chunk's A operands: step (tap, i) is packed step tap * 16 + q * CK / 4 + i
+  auto fetch_w = [&](float* dst, int q) {
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+      for (int i = 0; i < CK / 4; ++i) dst[tap * (CK / 4) + i] = wp[(tap * 16 + q * (CK / 4) + i) * 64];
+  };
+  fetch_w(wr, 0);
+  fetch(0);
+
+#pragma unroll 1
+  for (int q = 0; q < Q::NCK; ++q) {
+    // ---- channels q * CK .. of the group: registers -> LDS ----
+    if (q) __syncthreads();                        // every wave has read the previous chunk
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k)
+      if (loff[k] >= 0) {
+#pragma unroll
+        for (int c = 0; c < CK; ++c) tile[c * PLANE + loff[k]] = pre[k][c];
+      }
+    __syncthreads();
+    float wn[KC];
+    if (q + 1 < Q::NCK) {                          // uniform
+      fetch(q + 1);
+      fetch_w(wn, q + 1);
+    } else {
+#pragma unroll
+      for (int k = 0; k < KC; ++k) wn[k] = wr[k];
+    }
+
+    // ---- pairs of pixel rows: one A operand, two accumulator chains ----
+#pragma unroll
+    for (int rp = 0; rp < TR / 2; ++rp) {
+      if (oy0 + 2 * rp >= a.OH) continue;          // wave-uniform: rows below the map
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int i = 0; i < CK / 4; ++i) {
+          const int off = 4 * i * PLANE + (tap / 3) * CP + (tap % 3);
+          const float b0 = base[off + (2 * rp * S) * CP];
+          const float b1 = base[off + ((2 * rp + 1) * S) * CP];
+          acc[rp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[tap * (CK / 4) + i], b0, acc[rp][0], 0, 0, 0);
+          acc[rp][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[tap * (CK / 4) + i], b1, acc[rp][1], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k) wr[k] = wn[k];
+  }
+
+  const int ox = ox0 + j;
+  if (ox >= a.OW) return;
+#pragma unroll
+  for (int rp = 0; rp < TR / 2; ++rp)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int oy = oy0 + 2 * rp + h;
+      if (oy >= a.OH) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ch = g * CG + wave * 16 + kk * 4 + e;     // C/D layout of 16x16x4: row = 4 * (lane / 16) + e
+        float v = acc[rp][h][e] + (a.bias ? a.bias[ch] : 0.0f);
+        if (a.relu) v = fmaxf(v, 0.0f);
+        a.y[(((long long)n * a.C + ch) * a.OH + oy) * a.OW + ox] = v;
+      }
+    }
+}
+
+int launch64(GArgs a, int stride, hipStream_t s) {
+  a.gblocks = a.G;
+  const long long blocks = (long long)a.N * a.G * a.tiles_y * a.tiles_x;
+  if (blocks >= (1LL << 31)) return SSAD_E_BADARG;
+  const dim3 grid((unsigned)blocks);
+  if (stride == 1) hipLaunchKernelGGL((grouped_conv3x3_cg64_kernel<1>), grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL((grouped_conv3x3_cg64_kernel<2>), grid, dim3(kThreads), 0, s, a);
+  return (int)hipGetLastError();
+}
+
 template <int CG>
 int pack(const float* w, float* out, int G, hipStream_t s) {
   const long long total = (long long)G * Geo<CG>::MT * Geo<CG>::KS * 64;
@@ -168,7 +321,7 @@ extern "C" {
 long long ssad_grouped_conv3x3_filter_floats(int C, int group) {
   if (C < 1 || group < 1 || C % group) return -1;
   const int cg = C / group;
-  if (cg != 4 && cg != 8 && cg != 16 && cg != 32) return -1;
+  if (cg != 4 && cg != 8 && cg != 16 && cg != 32 && cg != 64) return -1;
   return (long long)group * (cg > 16 ? cg / 16 : 1) * (9 * cg / 4) * 64;
 }
 
@@ -179,14 +332,15 @@ int ssad_grouped_conv3x3_pack_filter(const float* w, int C, int group, float* pa
     case 4: return pack<4>(w, packed, group, s);
     case 8: return pack<8>(w, packed, group, s);
     case 16: return pack<16>(w, packed, group, s);
-    default: return pack<32>(w, packed, group, s);
+    case 32: return pack<32>(w, packed, group, s);
+    default: return pack<64>(w, packed, group, s);
   }
 }
 
 int ssad_grouped_conv3x3_forward(const float* x, const float* packed, const float* bias, int N, int C, int H,
                                  int W, int group, int stride, int relu, float* y, ssad_stream_t stream) {
   if (!x || !packed || !y || N < 0 || H < 1 || W < 1) return SSAD_E_BADARG;
-  if (ssad_grouped_conv3x3_filter_floats(C, group) < 0) return SSAD_E_BADARG;   // widths other than 4/8/16/32
+  if (ssad_grouped_conv3x3_filter_floats(C, group) < 0) return SSAD_E_BADARG;   // widths other than 4/8/16/32/64
   if (stride != 1 && stride != 2) return SSAD_E_BADARG;
   GArgs a;
   a.x = x; a.wp = packed; a.bias = bias; a.y = y;
@@ -200,7 +354,8 @@ int ssad_grouped_conv3x3_forward(const float* x, const float* packed, const floa
     case 4: return launch<4>(a, stride, s);
     case 8: return launch<8>(a, stride, s);
     case 16: return launch<16>(a, stride, s);
-    default: return launch<32>(a, stride, s);
+    case 32: return launch<32>(a, stride, s);
+    default: return launch64(a, stride, s);
   }
 }
 

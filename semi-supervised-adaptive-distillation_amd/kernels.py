@@ -1333,7 +1333,7 @@ def grouped_conv3x3_pack_filter(w, group, out=None):
     Cc = w.shape[0]
     n = lib().ssad_grouped_conv3x3_filter_floats(Cc, group)
     if n < 0 or w.shape[1] * group != Cc:
-        raise KernelError("grouped_conv3x3: %d channels in %d groups (4, 8, 16 or 32 per group)" % (Cc, group))
+        raise KernelError("grouped_conv3x3: %d channels in %d groups (4, 8, 16, 32 or 64 per group)" % (Cc, group))
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device="cuda")
     _check(lib().ssad_grouped_conv3x3_pack_filter(_ptr(w), Cc, group, _ptr(out), _stream()), "grouped pack")

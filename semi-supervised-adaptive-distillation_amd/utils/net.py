@@ -256,7 +256,7 @@ def save_model_to_weights_file(weights_file, store, cfg_yaml=""):
 # ResNet / ResNeXt-FPN backbones
 # ---------------------------------------------------------------------------
 
-_BLOCKS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3)}
+_BLOCKS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3), "x101-32x8d": (3, 4, 23, 3)}
 
 
 class WeightsWidthError(ValueError):
@@ -269,17 +269,28 @@ def check_backbone_widths(blobs, arch, channel_ratio=1.0, prefix=""):
     width-scaled filter present (all but the stem, which no ratio scales) has another shape than the network of
     `channel_ratio`.  One odd blob among matching ones is not that: it is reported and skipped by the loaders as the
     reference does (net.py:106-119)."""
-    from ..backbone_pipeline import NativeResNetFPN
+    from ..backbone_pipeline import GROUPED, NativeResNetFPN
     shapes = NativeResNetFPN.layer_shapes(arch, channel_ratio)
     names = backbone_blob_names(arch, channel_ratio)
     seen, bad = 0, []
+    seen_g, bad_g = 0, []              # the grouped 3x3 filters (branch2b) of a ResNeXt
     for layer, (wn, _, _) in names.items():
         if layer == "stem.0" or prefix + wn not in blobs:
             continue
         seen += 1
+        grouped = arch in GROUPED and layer.endswith(".c2")
+        seen_g += grouped
         have = tuple(np.asarray(blobs[prefix + wn]).shape)
         if have != shapes[layer]:
             bad.append((prefix + wn, have, shapes[layer]))
+            if grouped:
+                bad_g.append(bad[-1])
+    # two ResNeXts of one depth (64x4d, 32x8d) share every pointwise width: they differ in the grouped filters alone
+    if seen_g and len(bad_g) == seen_g and len(bad) == len(bad_g):
+        n, have, want = bad_g[0]
+        raise WeightsWidthError(
+            "the weights file was written for another ResNeXt than %s: %s has shape %s in the file, the %s network "
+            "has %s (and so for all %d grouped 3x3 filters present)" % (arch, n, have, arch, want, seen_g))
     if seen and len(bad) == seen:
         n, have, want = bad[0]
         raise WeightsWidthError(
