@@ -821,6 +821,47 @@ SSAD_API int ssad_retinanet_detect_class_specific(
     int* count_out, void* workspace, size_t workspace_bytes, ssad_stream_t stream,
     const ssad_detect_post* post, int class_specific_bbox);
 
+/* ssad_retinanet_detect (class_specific = 0) / ssad_retinanet_detect_class_specific without post options
+ * (class_specific = 1) for N images in one call: the same rows, bit for bit, as N calls on the images' slices, with a
+ * number of launches that does not depend on N and no host round trip.
+ *   cls_prob_host[l]  device float [N][A*C][H_l][W_l];  box_pred_host[l]  device float [N][A*4 (*C)][H_l][W_l]
+ *   im_scale_host / im_height_host / im_width_host   HOST arrays of N, read before the call returns
+ *   dets_out     device float [N][dets_per_im][6], rows from an image's count on are +0.0
+ *   counts_out   device int [N]
+ *   overflow_out device int [N]: nonzero when a level of the image had more than candidate_cap candidates.  The
+ *                rows and the count of such an image are unspecified (nothing is written out of bounds): run the
+ *                per-image entry on it.
+ * Instead of one key per score, one pass streams the scores and appends the key of every candidate (score >
+ * inference_th; > 0 on the last level; never a NaN) to the list of its (image, level), candidate_cap slots long; one
+ * workgroup per list then selects and orders its pre_nms_topn largest keys.  From there on the stages are
+ * ssad_retinanet_detect's, with the image on the grid.  Every counter is zeroed by the call itself.
+ * SSAD_E_BADARG, before any launch, for: a null pointer, N outside [1, SSAD_DETECT_BATCH_MAX_IMAGES], what
+ * ssad_retinanet_detect refuses, pre_nms_topn > SSAD_DETECT_BATCH_MAX_TOPN, candidate_cap < pre_nms_topn,
+ * dets_per_im > levels * pre_nms_topn, an im_scale that is not > 0, class_specific outside {0, 1}, or
+ * N * levels * candidate_cap at or above 2^31 (the only 32-bit offset that the limits above do not bound; tensor
+ * offsets are 64-bit).  SSAD_E_WORKSPACE for a workspace below
+ * ssad_retinanet_detect_batch_workspace_bytes (0 = unsupported geometry). */
+#define SSAD_DETECT_BATCH_MAX_IMAGES 64
+#define SSAD_DETECT_BATCH_MAX_TOPN 4096
+SSAD_API size_t ssad_retinanet_detect_batch_workspace_bytes(
+    int N, int levels, int A, int C, const int* H_host, const int* W_host, int pre_nms_topn, int candidate_cap);
+SSAD_API int ssad_retinanet_detect_batch(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int N, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, int candidate_cap, float nms_thresh,
+    int dets_per_im, const float* im_scale_host, const int* im_height_host, const int* im_width_host,
+    float bbox_xform_clip, int class_specific, float* dets_out, int* counts_out, int* overflow_out,
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream);
+/* Detections as ground truth for ssad_retinanet_anchor_labels (the teacher's pseudo-labels on unlabelled images,
+ * DISTILLATION.UNLABEL_DATASETS).  Per image n: the rows r < counts[n] of dets [N][dets_per_im][6] with
+ * score >= score_thresh, in their order, the first Gmax of them:
+ *   gt_boxes [N][Gmax][4] = box * im_scale[n] (float32, rounded once: blob pixels),  gt_classes [N][Gmax] = (int)class
+ *   (1-based),  gt_counts [N] = rows kept; rows from it on are zero.  im_scale is a DEVICE array of N.
+ * SSAD_E_BADARG for a null pointer or N, dets_per_im or Gmax < 1. */
+SSAD_API int ssad_detections_to_gt(const float* dets, const int* counts, const float* im_scale, int N,
+                                   int dets_per_im, float score_thresh, int Gmax, float* gt_boxes,
+                                   int* gt_classes, int* gt_counts, ssad_stream_t stream);
+
 /* COCO box evaluation on the device (detectron/lib/datasets/vid_eval.py: evaluateImg :236-318, accumulate
  * :320-425; driven for boxes by vid_dataset_evaluator.py:192-197).  useCats = 1, iouType 'bbox' only.
  *

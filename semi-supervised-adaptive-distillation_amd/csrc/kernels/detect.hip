@@ -29,10 +29,9 @@
 #include <stdint.h>
 
 #include "ssad_kernels.h"
+#include "detect_common.h"     // the decode, the rank sort and stages 3-5, shared with detect_batch.hip
 
 namespace {
-
-constexpr int kT = 256;
 
 struct DArgs {
   const float* prob[SSAD_MAX_LEVELS];     // [1][A*C][H][W]
@@ -139,34 +138,6 @@ __global__ __launch_bounds__(kT) void det_select_compact_kernel(const DArgs p, c
   }
 }
 
-// Rank sort of `segs` segments of seg_len keys each (blockIdx.y = segment): out[rank] = key, rank = the number of keys
-// that precede it (descending: larger first; ascending: smaller first; equal keys in index order -- stable).  vals
-// (may be null) travel with their keys.  O(seg_len^2) comparisons through LDS tiles.
-__global__ __launch_bounds__(kT) void det_rank_sort_kernel(const unsigned long long* in, const int* vals_in, int seg_len,
-                                                           int descending, unsigned long long* out, int* vals_out) {
-  __shared__ unsigned long long tile[kT];
-  const long long base = (long long)blockIdx.y * seg_len;
-  const int i = blockIdx.x * kT + threadIdx.x;
-  const unsigned long long mine = i < seg_len ? in[base + i] : 0;
-  int rank = 0;
-  for (int j0 = 0; j0 < seg_len; j0 += kT) {
-    const int j = j0 + threadIdx.x;
-    tile[threadIdx.x] = j < seg_len ? in[base + j] : 0;
-    __syncthreads();
-    const int m = seg_len - j0 < kT ? seg_len - j0 : kT;
-    for (int u = 0; u < m; ++u) {
-      const unsigned long long o = tile[u];
-      const bool before = descending ? (o > mine) : (o < mine);
-      rank += (before || (o == mine && j0 + u < i)) ? 1 : 0;
-    }
-    __syncthreads();
-  }
-  if (i < seg_len) {
-    out[base + rank] = mine;
-    if (vals_in) vals_out[base + rank] = vals_in[base + i];
-  }
-}
-
 // slot = l * topn + r: the r-th best element of level l
 __global__ __launch_bounds__(kT) void det_decode_kernel(const DArgs p,
                                                         const unsigned long long* keys,
@@ -175,177 +146,11 @@ __global__ __launch_bounds__(kT) void det_decode_kernel(const DArgs p,
   const int slot = blockIdx.x * kT + threadIdx.x;
   if (slot >= p.n) return;
   const int l = slot / p.topn;
-  const unsigned long long key = keys[slot];       // the level's r-th largest key (0 past its last element)
-  const unsigned sb = (unsigned)((key >> 29) & 0xffffffffull);
   cvals[slot] = slot;
-  if (sb == 0) {                                   // not a candidate
-    ckeys[slot] = ~0ull;                           // sorts last
-    scores[slot] = 0.0f;
-    return;
-  }
-  const int idx = (int)((~(unsigned)key) & 0x1fffffffu);
-  const int H = p.H[l], W = p.W[l], HW = H * W;
-  const int x = idx % W, y = (idx / W) % H;
-  const int ac = idx / HW;                         // a * C + cls
-  const int a = ac / p.C, cls = ac - a * p.C;
-  const float stride = (float)(1 << (p.k_min + l));
-  const double* c = p.cells + ((long long)l * p.A + a) * 4;
-  // boxes = float32([x, y, x, y]) * stride; boxes += cell_anchor (float64 add, float32 store)
-  const float bx = __fmul_rn((float)x, stride), by = __fmul_rn((float)y, stride);
-  const float b0 = (float)((double)bx + c[0]), b1 = (float)((double)by + c[1]);
-  const float b2 = (float)((double)bx + c[2]), b3 = (float)((double)by + c[3]);
-  // class-agnostic: channels 4a .. 4a+3; class-specific: the box of (anchor, class), the layout the training loss
-  // addresses (retinanet.py:140-151)
-  const long long ch = p.class_specific ? (long long)a * 4 * p.C + 4 * cls : (long long)a * 4;
-  const float* d = p.delta[l] + ch * HW + (long long)y * W + x;
-  const float dx = d[0], dy = d[HW], dw = fminf(d[2 * HW], p.xform_clip),
-              dh = fminf(d[3 * HW], p.xform_clip);
-  const float w = __fadd_rn(__fsub_rn(b2, b0), 1.0f), h = __fadd_rn(__fsub_rn(b3, b1), 1.0f);
-  const float cx = __fadd_rn(b0, __fmul_rn(0.5f, w)), cy = __fadd_rn(b1, __fmul_rn(0.5f, h));
-  const float pcx = __fadd_rn(__fmul_rn(dx, w), cx), pcy = __fadd_rn(__fmul_rn(dy, h), cy);
-  const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
-  float o0 = __fsub_rn(pcx, __fmul_rn(0.5f, pw));
-  float o1 = __fsub_rn(pcy, __fmul_rn(0.5f, ph));
-  float o2 = __fsub_rn(__fadd_rn(pcx, __fmul_rn(0.5f, pw)), 1.0f);
-  float o3 = __fsub_rn(__fadd_rn(pcy, __fmul_rn(0.5f, ph)), 1.0f);
-  o0 = __fdiv_rn(o0, p.scale); o1 = __fdiv_rn(o1, p.scale);
-  o2 = __fdiv_rn(o2, p.scale); o3 = __fdiv_rn(o3, p.scale);
-  const float xm = (float)(p.im_w - 1), ym = (float)(p.im_h - 1);
-  o0 = fmaxf(fminf(o0, xm), 0.0f); o1 = fmaxf(fminf(o1, ym), 0.0f);
-  o2 = fmaxf(fminf(o2, xm), 0.0f); o3 = fmaxf(fminf(o3, ym), 0.0f);
-  float* bo = boxes + (long long)slot * 4;
-  bo[0] = o0; bo[1] = o1; bo[2] = o2; bo[3] = o3;
-  scores[slot] = __uint_as_float(sb);
-  // ascending sort: class, then score descending, then slot
-  ckeys[slot] = ((unsigned long long)cls << 48) | ((unsigned long long)(~sb) << 16) |
-                (unsigned long long)(slot & 0xffff);
+  // keys[slot]: the level's r-th largest key (0 past its last element)
+  det_decode_candidate(keys[slot], slot, l, p.H[l], p.W[l], p.A, p.C, p.k_min, p.cells, p.delta[l], p.class_specific,
+                       p.xform_clip, p.scale, p.im_h, p.im_w, boxes + (long long)slot * 4, scores + slot, ckeys + slot);
 }
-
-// gather boxes / scores / classes into class-sorted order
-__global__ __launch_bounds__(kT) void det_gather_kernel(int n, const unsigned long long* skeys,
-                                                        const int* svals, const float* boxes,
-                                                        const float* scores, float* sboxes,
-                                                        float* sscores, int* scls) {
-  const int i = blockIdx.x * kT + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long k = skeys[i];
-  const int slot = svals[i];
-  scls[i] = k == ~0ull ? -1 : (int)(k >> 48);
-  sscores[i] = scores[slot];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sboxes[(long long)i * 4 + j] = boxes[(long long)slot * 4 + j];
-}
-
-// cython_nms.pyx:72-79, float32
-__device__ __forceinline__ bool suppresses(const float* a, float aarea, const float* b, float barea,
-                                           float thresh) {
-  const float xx1 = fmaxf(a[0], b[0]), yy1 = fmaxf(a[1], b[1]);
-  const float xx2 = fminf(a[2], b[2]), yy2 = fminf(a[3], b[3]);
-  const float w = fmaxf(0.0f, __fadd_rn(__fsub_rn(xx2, xx1), 1.0f));
-  const float h = fmaxf(0.0f, __fadd_rn(__fsub_rn(yy2, yy1), 1.0f));
-  const float inter = __fmul_rn(w, h);
-  const float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(aarea, barea), inter));
-  return ovr >= thresh;
-}
-
-__device__ __forceinline__ float box_area(const float* b) {
-  return __fmul_rn(__fadd_rn(__fsub_rn(b[2], b[0]), 1.0f), __fadd_rn(__fsub_rn(b[3], b[1]), 1.0f));
-}
-
-// mask[i][bj] bit t: box i suppresses box bj*64+t (same class, later in score order)
-__global__ __launch_bounds__(64) void det_nms_mask_kernel(int n, int words, const float* sboxes,
-                                                          const int* scls, float thresh,
-                                                          unsigned long long* mask) {
-  __shared__ float jb[64][4];
-  __shared__ int jc[64];
-  const int bi = blockIdx.y, bj = blockIdx.x;
-  if (bj < bi) return;
-  const int t = threadIdx.x;
-  const int j = bj * 64 + t;
-  if (j < n) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) jb[t][q] = sboxes[(long long)j * 4 + q];
-    jc[t] = scls[j];
-  } else {
-    jc[t] = -2;
-  }
-  __syncthreads();
-  const int i = bi * 64 + t;
-  if (i >= n) return;
-  const int ci = scls[i];
-  unsigned long long bits = 0;
-  if (ci >= 0) {
-    float ib[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ib[q] = sboxes[(long long)i * 4 + q];
-    const float ia = box_area(ib);
-    for (int u = 0; u < 64; ++u) {
-      const int jj = bj * 64 + u;
-      if (jj > i && jc[u] == ci && suppresses(ib, ia, jb[u], box_area(jb[u]), thresh))
-        bits |= 1ull << u;
-    }
-  }
-  mask[(long long)i * words + bj] = bits;
-}
-
-// one workgroup per class: greedy walk of the class segment in score order
-__global__ __launch_bounds__(kT) void det_nms_scan_kernel(int n, int words, int C, const int* scls,
-                                                          const float* sscores,
-                                                          const unsigned long long* mask,
-                                                          unsigned long long* fkeys) {
-  extern __shared__ unsigned long long remv[];
-  __shared__ int seg[2];
-  const int cls = blockIdx.x;
-  for (int w = threadIdx.x; w < words; w += kT) remv[w] = 0;
-  if (threadIdx.x == 0) {
-    // segment of this class in the class-sorted arrays (binary searches)
-    int lo = 0, hi = n;
-    while (lo < hi) { const int m = (lo + hi) >> 1; const int c = scls[m]; if (c >= 0 && c < cls) lo = m + 1; else hi = m; }
-    seg[0] = lo;
-    hi = n;
-    while (lo < hi) { const int m = (lo + hi) >> 1; const int c = scls[m]; if (c >= 0 && c <= cls) lo = m + 1; else hi = m; }
-    seg[1] = lo;
-  }
-  __syncthreads();
-  const int s = seg[0], e = seg[1];
-  for (int i = s; i < e; ++i) {
-    const bool removed = (remv[i >> 6] >> (i & 63)) & 1ull;      // uniform read
-    __syncthreads();
-    if (!removed) {
-      for (int w = threadIdx.x + (i >> 6); w < words; w += kT) remv[w] |= mask[(long long)i * words + w];
-      if (threadIdx.x == 0)   // descending sort key: score, then earlier position first
-        fkeys[i] = ((unsigned long long)__float_as_uint(sscores[i]) << 32) |
-                   (unsigned long long)(~(unsigned)i);
-    } else if (threadIdx.x == 0) {
-      fkeys[i] = 0;
-    }
-    __syncthreads();
-  }
-  (void)C;
-}
-
-__global__ __launch_bounds__(kT) void det_emit_kernel(int n, int dets_per_im,
-                                                      const unsigned long long* fsorted,
-                                                      const float* sboxes, const int* scls,
-                                                      float* out, int* count) {
-  const int r = blockIdx.x * kT + threadIdx.x;
-  if (r == 0) {
-    int c = 0;
-    while (c < dets_per_im && c < n && fsorted[c] != 0) ++c;
-    *count = c;
-  }
-  if (r >= dets_per_im || r >= n) return;
-  const unsigned long long k = fsorted[r];
-  float* o = out + (long long)r * 6;
-  if (k == 0) { for (int j = 0; j < 6; ++j) o[j] = 0.0f; return; }
-  const int i = (int)(~(unsigned)k);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = sboxes[(long long)i * 4 + j];
-  o[4] = __uint_as_float((unsigned)(k >> 32));
-  o[5] = (float)(scls[i] + 1);                  // class ids are 1-based in the output
-}
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Plan {
   long long total;

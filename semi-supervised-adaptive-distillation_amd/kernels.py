@@ -302,6 +302,11 @@ def lib():
     L.ssad_box_voting.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, f32, vp, vp, vp]
     L.ssad_retinanet_detect_ex_workspace_bytes.restype = sz
     L.ssad_retinanet_detect_ex_workspace_bytes.argtypes = [i32, i32, i32, vp, vp, i32, C.POINTER(DetectPost)]
+    L.ssad_retinanet_detect_batch_workspace_bytes.restype = sz
+    L.ssad_retinanet_detect_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32]
+    L.ssad_retinanet_detect_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, i32, i32, f32, i32,
+                                              vp, vp, vp, f32, i32, vp, vp, vp, vp, sz, vp]
+    L.ssad_detections_to_gt.argtypes = [vp, vp, vp, i32, i32, f32, i32, vp, vp, vp, vp]
     L.ssad_kernels_arch.restype = C.c_char_p
     L.ssad_kernels_abi_version.restype = i32
     if L.ssad_kernels_abi_version() != ABI_VERSION:

@@ -230,3 +230,135 @@ class RetinanetDetector(object):
         if rc:
             raise K.KernelError("retinanet_detect failed (%d)" % rc)
         return self.out[:int(self.count.item())]
+
+
+class BatchedRetinanetDetector(object):
+    """`RetinanetDetector` for a minibatch: N images per call, one kernel sequence whose length does not depend on N
+    (ssad_retinanet_detect_batch), no Soft-NMS / voting / softmax options.
+
+    `__call__(cls_probs, box_preds, im_heights, im_widths, im_scales)` takes the per-level sigmoid scores
+    [N][A*C][H][W] and box deltas [N][A*4][H][W] ([N][A*4*C][H][W] with `class_specific_bbox=True`) as device tensors
+    -- what DistillHeads leaves in t_prob / t_bbox -- and three host sequences of N.  It returns
+    (dets float32 [N][dets_per_im][6], counts int32 [N]): image n's rows are dets[n, :counts[n]], bit for bit the rows
+    RetinanetDetector gives on the [n:n+1] slices; rows from counts[n] on are zero.  Both tensors are this object's
+    buffers: the next call overwrites them.
+
+    Only scores above the threshold become sort keys, in lists of `candidate_capacity` keys per (image, level).  An
+    image with a fuller level is reported by the kernels; `__call__` reads those N flags (the one device-to-host copy
+    of a call), runs the per-image detector on each flagged image's slices and stores that result in its row:
+    `last_fallback` lists them.  So the capacity decides speed, never the result.  The default (None) is
+    max(4 * pre_nms_topn, min(scores of one image on the last level, 65536)): the last level's threshold is 0, so on
+    sigmoid scores its list holds the whole level.
+
+    `pseudo_labels(dets, counts, im_scales, score_thresh, Gmax)` turns detections into the labeller's ground truth:
+    (gt_boxes float32 [N][Gmax][4] in blob pixels, gt_classes int32 [N][Gmax], gt_counts int32 [N]), device tensors
+    for RetinanetLabeler.__call__ (ssad_detections_to_gt)."""
+
+    DEFAULT_CAPACITY_LIMIT = 1 << 16
+
+    def __init__(self, N, level_shapes, cfg=AnchorConfig, inference_th=0.05, pre_nms_topn=1000,
+                 nms_thresh=0.5, dets_per_im=100, device="cuda", *, class_specific_bbox=False,
+                 candidate_capacity=None):
+        if not isinstance(class_specific_bbox, (bool, np.bool_)):
+            raise K.KernelError("class_specific_bbox= is a boolean")
+        self.class_specific_bbox = bool(class_specific_bbox)
+        self.N, self.cfg, self.device = int(N), cfg, device
+        self.shapes = [(int(h), int(w)) for h, w in level_shapes]
+        self.levels = len(self.shapes)
+        self.A = cfg.scales_per_octave * len(cfg.aspect_ratios)
+        self.C = cfg.num_classes - 1
+        self.th, self.topn, self.nms, self.keep = inference_th, int(pre_nms_topn), nms_thresh, int(dets_per_im)
+        if self.N < 1 or self.levels < 1:
+            raise K.KernelError("BatchedRetinanetDetector needs N >= 1 images and at least one level")
+        if candidate_capacity is None:
+            last = self.A * self.C * self.shapes[-1][0] * self.shapes[-1][1]
+            candidate_capacity = max(4 * self.topn, min(last, self.DEFAULT_CAPACITY_LIMIT))
+        self.capacity = int(candidate_capacity)
+        if self.capacity < self.topn:
+            raise K.KernelError("candidate_capacity %d is below pre_nms_topn %d" % (self.capacity, self.topn))
+        IntArr = C.c_int * self.levels
+        self._H = IntArr(*[h for h, _ in self.shapes])
+        self._W = IntArr(*[w for _, w in self.shapes])
+        nb = K.lib().ssad_retinanet_detect_batch_workspace_bytes(self.N, self.levels, self.A, self.C, self._H,
+                                                                 self._W, self.topn, self.capacity)
+        if nb == 0:
+            raise K.KernelError("retinanet_detect_batch: unsupported geometry")
+        self.cells = torch.as_tensor(cell_anchors(cfg)[:self.levels], dtype=torch.float64,
+                                     device=device).contiguous()
+        self.ws = torch.empty(int(nb), dtype=torch.uint8, device=device)
+        self.out = torch.zeros((self.N, self.keep, 6), dtype=torch.float32, device=device)
+        self.counts = torch.zeros(self.N, dtype=torch.int32, device=device)
+        self.overflow = torch.zeros(self.N, dtype=torch.int32, device=device)
+        self.last_fallback = []
+        self._single = None
+
+    def _check_inputs(self, cls_probs, box_preds, im_heights, im_widths, im_scales):
+        if len(cls_probs) != self.levels or len(box_preds) != self.levels:
+            raise K.KernelError("one cls_prob and one box_pred tensor per level (%d)" % self.levels)
+        box_ch = self.A * 4 * (self.C if self.class_specific_bbox else 1)
+        for t, (h, w) in zip(cls_probs, self.shapes):
+            if tuple(t.shape) != (self.N, self.A * self.C, h, w) or t.dtype != torch.float32 or \
+                    not t.is_contiguous() or not t.is_cuda:
+                raise K.KernelError("cls_prob must be N x A*C x H x W contiguous float32 device tensors")
+        for t, (h, w) in zip(box_preds, self.shapes):
+            if tuple(t.shape) != (self.N, box_ch, h, w) or t.dtype != torch.float32 or \
+                    not t.is_contiguous() or not t.is_cuda:
+                raise K.KernelError("box_pred must be N x %s x H x W contiguous float32 device tensors"
+                                    % ("A*4*C" if self.class_specific_bbox else "A*4"))
+        if len(im_heights) != self.N or len(im_widths) != self.N or len(im_scales) != self.N:
+            raise K.KernelError("im_heights, im_widths and im_scales are host sequences of N = %d" % self.N)
+        if not all(float(s) > 0 for s in im_scales):
+            raise K.KernelError("every im_scale must be positive")
+
+    def __call__(self, cls_probs, box_preds, im_heights, im_widths, im_scales):
+        self._check_inputs(cls_probs, box_preds, im_heights, im_widths, im_scales)
+        PtrArr = C.c_void_p * self.levels
+        rc = K.lib().ssad_retinanet_detect_batch(
+            PtrArr(*[t.data_ptr() for t in cls_probs]), PtrArr(*[t.data_ptr() for t in box_preds]),
+            C.c_void_p(self.cells.data_ptr()), self.N, self.levels, self.A, self.C, self.cfg.k_min, self._H, self._W,
+            self.th, self.topn, self.capacity, self.nms, self.keep,
+            (C.c_float * self.N)(*[float(s) for s in im_scales]), (C.c_int * self.N)(*[int(h) for h in im_heights]),
+            (C.c_int * self.N)(*[int(w) for w in im_widths]), float(np.log(1000. / 16.)),
+            int(self.class_specific_bbox), C.c_void_p(self.out.data_ptr()), C.c_void_p(self.counts.data_ptr()),
+            C.c_void_p(self.overflow.data_ptr()), C.c_void_p(self.ws.data_ptr()), self.ws.numel(), K._stream())
+        if rc:
+            raise K.KernelError("retinanet_detect_batch failed (%d)" % rc)
+        self.last_fallback = [int(n) for n in torch.nonzero(self.overflow).flatten().cpu().numpy()]
+        for n in self.last_fallback:
+            if self._single is None:
+                self._single = RetinanetDetector(self.shapes, self.cfg, self.th, self.topn, self.nms, self.keep,
+                                                 self.device, class_specific_bbox=self.class_specific_bbox)
+            # slices of an [N][ch][H][W] tensor are contiguous; the detector's own buffers hold all dets_per_im rows
+            self._single([t[n:n + 1] for t in cls_probs], [t[n:n + 1] for t in box_preds],
+                         im_heights[n], im_widths[n], im_scales[n])
+            self.out[n].copy_(self._single.out)
+            self.counts[n:n + 1].copy_(self._single.count)
+        return self.out, self.counts
+
+    def pseudo_labels(self, dets, counts, im_scales, score_thresh, Gmax):
+        if tuple(dets.shape) != (self.N, self.keep, 6) or dets.dtype != torch.float32 or not dets.is_contiguous() \
+                or not dets.is_cuda:
+            raise K.KernelError("dets must be the N x dets_per_im x 6 contiguous float32 device tensor of __call__")
+        if tuple(counts.shape) != (self.N,) or counts.dtype != torch.int32 or not counts.is_contiguous() \
+                or not counts.is_cuda:
+            raise K.KernelError("counts must be the contiguous int32 device tensor [N] of __call__")
+        if not torch.is_tensor(im_scales):
+            if len(im_scales) != self.N:
+                raise K.KernelError("im_scales has one value per image (N = %d)" % self.N)
+            im_scales = torch.tensor([float(s) for s in im_scales], dtype=torch.float32, device=dets.device)
+        if tuple(im_scales.shape) != (self.N,) or im_scales.dtype != torch.float32 or not im_scales.is_contiguous() \
+                or not im_scales.is_cuda:
+            raise K.KernelError("im_scales must be N floats (a host sequence or a float32 device tensor)")
+        Gmax = int(Gmax)
+        if Gmax < 1:
+            raise K.KernelError("Gmax must be at least 1")
+        gt_boxes = torch.empty((self.N, Gmax, 4), dtype=torch.float32, device=dets.device)
+        gt_classes = torch.empty((self.N, Gmax), dtype=torch.int32, device=dets.device)
+        gt_counts = torch.empty(self.N, dtype=torch.int32, device=dets.device)
+        rc = K.lib().ssad_detections_to_gt(
+            C.c_void_p(dets.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(im_scales.data_ptr()), self.N,
+            self.keep, float(score_thresh), Gmax, C.c_void_p(gt_boxes.data_ptr()), C.c_void_p(gt_classes.data_ptr()),
+            C.c_void_p(gt_counts.data_ptr()), K._stream())
+        if rc:
+            raise K.KernelError("detections_to_gt failed (%d)" % rc)
+        return gt_boxes, gt_classes, gt_counts

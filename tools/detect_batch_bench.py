@@ -1,0 +1,164 @@
+"""Times BatchedRetinanetDetector on a minibatch of 16 against 16 calls of RetinanetDetector, in one process, at the
+benchmark's config-3 level shapes (a 640 x 896 blob: 8.59 M scores an image, 80 classes, pre_nms_topn 1000), and
+writes profiles/detect_batch.md.
+
+Two inputs.  "sparse": every score uniform in (0.001, 0.04) except a share --share of them (default 0.1 %), uniform
+in (0.05, 1) -- what a trained head's Sigmoid leaves above inference_th = 0.05; the last level's threshold is 0, so
+all of its 25 200 scores are candidates, as on real maps.  "dense": uniform (0, 1) scores, every level of every image
+overflows its candidate list and the batched call runs the per-image path for all 16 images on top of its own
+launches: what the fallback costs.
+
+Timing: wall clock around the call(s) between two device synchronisations -- both paths read a few words back
+(the per-image detector its row count, 16 times; the batched one its N overflow flags, once), and that wait is part
+of what a caller pays.  The two paths alternate; a warm-up, then the median of --iters rounds.  The rows of the two
+paths are compared bit for bit before anything is timed.  Prints one JSON line.
+
+    python tools/detect_batch_bench.py [--iters 30] [--warmup 3] [--share 0.001] [--commit ID] [--out profiles/detect_batch.md]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(80, 112), (40, 56), (20, 28), (10, 14), (5, 7)]
+N, AC, TOPN = 16, 720, 1000
+IM_H, IM_W = 640, 896
+
+
+def commit_id():
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], text=True,
+                                       stderr=subprocess.DEVNULL).strip()
+    except Exception:
+        return "unknown"
+
+
+def traffic_bytes(cand_per_level, cap, topn=TOPN):
+    """bytes one image moves in the batched call, counted from detect_batch.hip / detect_common.h (not measured):
+    the scores once, a key per candidate, the top-k workgroups' passes over their lists, and the n-slot stages"""
+    scores = 4 * AC * sum(h * w for h, w in SHAPES)
+    keys = sum(8 * min(c, cap) for c in cand_per_level)
+    topk = sum(8 * min(c, cap) * (9 if c > topn else 1) for c in cand_per_level)      # 8 digit passes + compaction
+    n = len(SHAPES) * topn
+    words = (n + 63) // 64
+    # keys_s w+r, decode (boxes, scores, ckeys, cvals), two rank sorts (each block streams its segment: n/256 * n * 8),
+    # gather r+w, mask: boxes read per 64 x 64 tile + the upper triangle of n * words words written, scan + emit
+    stages = 16 * n + 36 * n + 2 * (n // 256 + 1) * n * 8 + 64 * n + (words * words // 2) * (64 * 20 + 64 * 8) + 24 * n
+    return scores, scores + keys + topk + stages
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--share", type=float, default=0.001)
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detect_batch.md"))
+    args = ap.parse_args()
+    import torch
+    import ssad_amd  # noqa: F401
+    from ssad_amd.roi_data.retinanet import BatchedRetinanetDetector, RetinanetDetector
+    if not torch.cuda.is_available():
+        raise SystemExit("detect_batch_bench needs a GPU: nothing is estimated without one")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rand = lambda *shape: torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32)
+    deltas = [torch.randn((N, 36, h, w), generator=gen, device="cuda") * 0.4 for h, w in SHAPES]
+    sparse = []
+    for h, w in SHAPES:
+        low, high = 0.001 + 0.039 * rand(N, AC, h, w), 0.05 + 0.95 * rand(N, AC, h, w)
+        sparse.append(torch.where(rand(N, AC, h, w) < args.share, high, low).contiguous())
+    dense = [rand(N, AC, h, w) for h, w in SHAPES]
+    above = sum(int((p > 0.05).sum()) for p in sparse) / float(sum(p.numel() for p in sparse))
+    cand = [[int((p[n] > (0.05 if l < len(SHAPES) - 1 else 0.0)).sum()) for l, p in enumerate(sparse)] for n in range(N)]
+
+    batch = BatchedRetinanetDetector(N, SHAPES)
+    single = RetinanetDetector(SHAPES)
+    sizes = ([IM_H] * N, [IM_W] * N, [1.0] * N)
+
+    def run_batch(probs):
+        return batch(probs, deltas, *sizes)
+
+    def run_loop(probs):
+        return [single([p[n:n + 1] for p in probs], [d[n:n + 1] for d in deltas], IM_H, IM_W, 1.0).clone()
+                for n in range(N)]
+
+    results, fallbacks = {}, {}
+    for name, probs in (("sparse", sparse), ("dense", dense)):
+        dets, counts = run_batch(probs)
+        fallbacks[name] = list(batch.last_fallback)
+        for n, rows in enumerate(run_loop(probs)):
+            assert int(counts[n]) == rows.shape[0] and torch.equal(dets[n, :rows.shape[0]].view(torch.int32),
+                                                                   rows.view(torch.int32)), (name, n)
+        for _ in range(args.warmup):
+            run_batch(probs), run_loop(probs)
+        t = {"batched": [], "loop": []}
+        for _ in range(args.iters):
+            for label, fn in (("batched", run_batch), ("loop", run_loop)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(probs)
+                torch.cuda.synchronize()
+                t[label].append((time.perf_counter() - t0) * 1e3)
+        for label, v in t.items():
+            results["%s | %s" % (name, label)] = [float(np.median(v)), float(np.min(v)), float(np.max(v))]
+    assert fallbacks["sparse"] == [] and fallbacks["dense"] == list(range(N)), fallbacks
+    ratio = results["sparse | loop"][0] / results["sparse | batched"][0]
+    ratio_dense = results["dense | loop"][0] / results["dense | batched"][0]
+    mean_cand = [int(np.mean([c[l] for c in cand])) for l in range(len(SHAPES))]
+    floor, moved = traffic_bytes(mean_cand, batch.capacity)
+    commit = args.commit or commit_id()
+    lines = [
+        "# Batched RetinaNet detection against the per-image loop",
+        "",
+        "`python tools/detect_batch_bench.py` on one MI355X, build %s: N = %d images, 5 levels of a 640 x 896 blob"
+        % (commit, N),
+        "(8.59 M scores an image), 80 classes, `pre_nms_topn` 1000, `dets_per_im` 100, `candidate_capacity` %d (the"
+        % batch.capacity,
+        "default).  One process; the batched call and the loop of %d `RetinanetDetector` calls alternate, %d warm-up"
+        % (N, args.warmup),
+        "rounds, median of %d; wall clock between two device synchronisations, so each path's read-backs count."
+        % args.iters,
+        "The rows of the two paths were compared bit for bit on both inputs before timing.",
+        "",
+        "Sparse input: %.4f %% of all scores above 0.05 (uniform in (0.05, 1)), the rest uniform in (0.001, 0.04);"
+        % (100.0 * above),
+        "candidates per image and level, mean: %s (the last level's threshold is 0).  `last_fallback == []`."
+        % ", ".join(str(c) for c in mean_cand),
+        "Dense input: uniform (0, 1) scores; every image overflows and takes the per-image path inside the batched call",
+        "(`last_fallback == [0 ... %d]`)." % (N - 1),
+        "",
+        "| input | path | median ms per %d images | min ... max |" % N,
+        "|---|---|---|---|",
+    ]
+    for key, (med, lo, hi) in results.items():
+        name, label = key.split(" | ")
+        lines.append("| %s | %s | %.3f | %.3f ... %.3f |" % (name, label, med, lo, hi))
+    lines += [
+        "",
+        "Sparse: the batched call is **%.2fx** the loop's speed (loop / batched).  Dense: %.2fx -- the fallback pays the"
+        % (ratio, ratio_dense),
+        "batched launches and then the whole loop.",
+        "",
+        "Bytes moved per image on the sparse input, counted from the kernels' code (not from counters): %.1f MB against"
+        % (moved / 1e6),
+        "the floor of reading every score once, %.1f MB: %.2fx the floor.  The per-image path moves about 0.7 GB"
+        % (floor / 1e6, moved / float(floor)),
+        "(a key per score written, then read by eight histogram passes and the compaction).",
+        "",
+        "This one same-process measurement is all the speed claim rests on; no ratio was fixed in advance.",
+    ]
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(json.dumps({"iters": args.iters, "commit": commit, "share_above_threshold": above,
+                      "median_min_max_ms": results, "loop_over_batched_sparse": ratio,
+                      "loop_over_batched_dense": ratio_dense, "bytes_per_image": moved, "floor_bytes": floor}))
+
+
+if __name__ == "__main__":
+    main()
