@@ -852,6 +852,33 @@ SSAD_API int ssad_retinanet_detect_batch(
     int dets_per_im, const float* im_scale_host, const int* im_height_host, const int* im_width_host,
     float bbox_xform_clip, int class_specific, float* dets_out, int* counts_out, int* overflow_out,
     void* workspace, size_t workspace_bytes, ssad_stream_t stream);
+/* ssad_retinanet_detect_batch with the per-image entries' remaining options; the rows are those of
+ * ssad_retinanet_detect_class_specific(post) on the images' slices, bit for bit, and the number of launches still does
+ * not depend on N.
+ *   post           as in ssad_retinanet_detect_ex (NULL, or greedy without voting: the launches of
+ *                  ssad_retinanet_detect_batch).  Soft-NMS runs one workgroup per (class, image), voting one wave per
+ *                  (candidate, image); both replace / follow the greedy stages exactly as in the per-image entry.
+ *   cls_is_logits  0: cls_prob_host[l] holds scores [N][A*C][H][W].  1: it holds the RETINANET.SOFTMAX head's cls_pred
+ *                  logits [N][A*(C+1)][H][W] (background first in every anchor's group; C is still the foreground
+ *                  count).  The candidate pass then computes each cell's softmax in registers -- the arithmetic of
+ *                  ssad_group_spatial_softmax, the same bits -- and appends the foreground classes above the threshold
+ *                  under the element index they have in the background-dropped [A*C][H][W] tensor; the probabilities
+ *                  are never written.  C + 1 must lie within ssad_group_spatial_softmax's class limits (2 .. 128).
+ * SSAD_E_BADARG, before any launch, for everything ssad_retinanet_detect_batch refuses, a post that
+ * ssad_retinanet_detect_ex refuses, cls_is_logits outside {0, 1}, or logits with C + 1 > 128.  Workspace:
+ * ssad_retinanet_detect_batch_ex_workspace_bytes = the plain size for a NULL / plain post, else plain + N x what the
+ * options add per image; 0 for unsupported geometry or an invalid post. */
+SSAD_API size_t ssad_retinanet_detect_batch_ex_workspace_bytes(
+    int N, int levels, int A, int C, const int* H_host, const int* W_host, int pre_nms_topn, int candidate_cap,
+    const ssad_detect_post* post);
+SSAD_API int ssad_retinanet_detect_batch_ex(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int N, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, int candidate_cap, float nms_thresh,
+    int dets_per_im, const float* im_scale_host, const int* im_height_host, const int* im_width_host,
+    float bbox_xform_clip, int class_specific, float* dets_out, int* counts_out, int* overflow_out,
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream, const ssad_detect_post* post,
+    int cls_is_logits);
 /* Detections as ground truth for ssad_retinanet_anchor_labels (the teacher's pseudo-labels on unlabelled images,
  * DISTILLATION.UNLABEL_DATASETS).  Per image n: the rows r < counts[n] of dets [N][dets_per_im][6] with
  * score >= score_thresh, in their order, the first Gmax of them:

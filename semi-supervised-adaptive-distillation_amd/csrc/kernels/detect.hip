@@ -203,28 +203,6 @@ size_t ssad_retinanet_detect_workspace_bytes(int levels, int A, int C, const int
 
 namespace {
 
-// what the post-processing options add behind the greedy path's workspace: pick ranks, Soft-NMS's own workspace,
-// the voted boxes
-size_t post_bytes(size_t n) { return al(n * 4) + al(ssad_soft_nms_workspace_bytes((int)n)) + al(n * 16); }
-
-bool post_is_plain(const ssad_detect_post* post) {
-  return !post || (post->nms_method == SSAD_NMS_GREEDY && !post->vote);
-}
-
-int check_post(const ssad_detect_post* post) {
-  if (!post) return 0;
-  if (post->nms_method < SSAD_NMS_GREEDY || post->nms_method > SSAD_NMS_SOFT_GAUSSIAN) return SSAD_E_BADARG;
-  if (post->nms_method != SSAD_NMS_GREEDY && !(post->sigma > 0.0f)) return SSAD_E_BADARG;
-  if (post->vote) {
-    const int m = post->scoring_method;
-    if (m < SSAD_VOTE_ID || m > SSAD_VOTE_QUASI_SUM) return SSAD_E_BADARG;
-    if ((m == SSAD_VOTE_TEMP_AVG || m == SSAD_VOTE_GENERALIZED_AVG || m == SSAD_VOTE_QUASI_SUM) &&
-        !(post->beta > 0.0f))
-      return SSAD_E_BADARG;
-  }
-  return 0;
-}
-
 // the body of ssad_retinanet_detect and ssad_retinanet_detect_ex; post == nullptr (or greedy without voting) makes
 // the launches ssad_retinanet_detect has always made
 int detect_body(

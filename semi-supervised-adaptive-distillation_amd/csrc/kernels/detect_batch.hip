@@ -12,12 +12,23 @@
 //   3. detect.hip's stages 2-5 (detect_common.h) with the image on the grid, the decode with per-image scale / size.
 // The keys are detect.hip's ([63:61] level order | [60:29] score bits | [28:0] ~index within the image's level), they
 // are unique, and every later stage orders them itself: the arrival order in a list does not reach the result.
+//
+// ssad_retinanet_detect_batch_ex adds the per-image entries' remaining options:
+//   - cls_is_logits: step 1 reads the softmax head's logits [N][A*(C+1)][H][W] instead (detb_candidates_logits_kernel):
+//     a lane holds one cell's C+1 logits in registers, softmax_cell.h's arithmetic -- group_softmax_kernel's, so the
+//     same bits -- makes its probabilities, and the foreground classes above the threshold are appended under the
+//     index they would have in the background-dropped [A*C][H][W] tensor.  The probabilities are never written;
+//   - Soft-NMS in place of the bit-matrix and the scan, and box voting before the final sort: soft_nms.hip's two
+//     kernels with the image on their grid (soft_nms_images.h), one launch each for the whole batch.
 
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 
 #include "ssad_kernels.h"
 #include "detect_common.h"
+#include "softmax_cell.h"
+#include "soft_nms_images.h"
 
 namespace {
 
@@ -26,7 +37,7 @@ constexpr int kCandIters = 8;    // 16-byte loads per lane the candidate pass ai
 constexpr int kCandMaxBlocks = 2048;   // per (image, level)
 
 struct BGeom {
-  const float* prob[SSAD_MAX_LEVELS];     // [N][A*C][H][W]
+  const float* prob[SSAD_MAX_LEVELS];     // [N][A*C][H][W]; from logits: [N][A*(C+1)][H][W]
   const float* delta[SSAD_MAX_LEVELS];    // [N][A*4][H][W]; class_specific: [N][A*4*C][H][W]
   const double* cells;                    // [levels][A][4]
   int H[SSAD_MAX_LEVELS], W[SSAD_MAX_LEVELS];
@@ -102,6 +113,52 @@ __global__ __launch_bounds__(kT) void detb_candidates_kernel(const BGeom g, int*
     else if (t < 6) { if (tail0 + (t - 3) < E) e = tail0 + (t - 3); }
     const float x = e >= 0 ? s[e] : 0.0f;
     push_candidates(e >= 0 && x > th, x, e, lb, counter, list, g.cap);
+  }
+}
+
+// The candidate pass on the softmax head's logits; same grid, a workgroup belongs to one (image, level).  Work item
+// = the softmax kernels': (anchor of the image, chunk of kT positions), one lane = one cell, whose C + 1 logits come
+// plane by plane at stride H*W (coalesced across the lanes, non-temporal: nobody reads them again).  bstart gives the
+// level min(items, kCandMaxBlocks) workgroups.  The wave stays whole around every vote: a lane past the plane's end
+// loads the plane's last cell and takes part with c = false.
+template <bool FAST, int CMAX>
+__global__ __launch_bounds__(kT) void detb_candidates_logits_kernel(const BGeom g, int* counts,
+                                                                    unsigned long long* cand) {
+  const int img = blockIdx.y;
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < SSAD_MAX_LEVELS; ++i)
+    if (i < g.levels && (int)blockIdx.x >= g.bstart[i]) l = i;
+  const int blk = blockIdx.x - g.bstart[l], nblk = g.bstart[l + 1] - g.bstart[l];
+  const int C = g.C, K = g.C + 1;                                 // foreground classes; logits of a cell
+  const unsigned hw = (unsigned)(g.H[l] * g.W[l]);
+  const int chunks = (int)((hw + kT - 1) / kT), items = g.A * chunks;
+  const float* x = g.prob[l] + (size_t)img * g.A * K * hw;
+  const float th = l == g.levels - 1 ? g.th_last : g.th;
+  const int seg = img * g.levels + l;
+  int* counter = counts + seg;
+  unsigned long long* list = cand + (long long)seg * g.cap;
+  const unsigned long long lb = (unsigned long long)(7 - l) << 61;
+  for (int item = blk; item < items; item += nblk) {              // uniform in the workgroup
+    const int a = item / chunks;
+    const unsigned pos = (unsigned)(item - a * chunks) * kT + threadIdx.x;
+    const bool in = pos < hw;
+    float v[CMAX];
+    load_cell<CMAX, true>(x + (size_t)a * K * hw, hw, in ? pos : hw - 1, K, -FLT_MAX, v);
+    softmax_cell<FAST, CMAX>(v);
+    // nearly every cell has no foreground class above the threshold: one vote for the cell-wave first
+    bool any = false;
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c) any = any || (c < K && v[c] > th);          // NaN: false
+    if (__ballot(in && any) == 0) continue;
+    const int e0 = a * C * (int)hw + (int)pos;                    // class 1's index in the [A*C][H][W] tensor
+    bool full = false;
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c) {
+      if (c < K && !full)                                         // wave-uniform
+        full = push_candidates(in && v[c] > th, v[c], e0 + (c - 1) * (int)hw, lb, counter, list, g.cap);
+    }
+    if (full) break;
   }
 }
 
@@ -261,32 +318,31 @@ size_t batch_bytes(const BPlan& p) {
          2 * al(p.slots) + al(p.slots * 4) + 2 * al(p.slots) + al(p.slots * 2 * (size_t)p.words) + 2 * al(p.slots * 2);
 }
 
-}  // namespace
+// what the options add behind batch_bytes: pick ranks, the scores of long Soft-NMS segments and the voted boxes of
+// all N images, carved below as three arrays of N * n slots (al(N * x) <= N * al(x))
+size_t batch_post_bytes(int N, const BPlan& p) { return (size_t)N * post_bytes((size_t)p.n); }
 
-extern "C" {
+bool logit_classes_ok(int C) { return C + 1 >= kMinClasses && C + 1 <= kMaxClasses; }
 
-size_t ssad_retinanet_detect_batch_workspace_bytes(int N, int levels, int A, int C, const int* H_host,
-                                                   const int* W_host, int pre_nms_topn, int candidate_cap) {
-  BPlan p;
-  if (batch_plan(N, levels, A, C, H_host, W_host, pre_nms_topn, candidate_cap, &p, nullptr)) return 0;
-  return batch_bytes(p);
-}
-
-int ssad_retinanet_detect_batch(
+// the body of ssad_retinanet_detect_batch and ssad_retinanet_detect_batch_ex; post == nullptr (or greedy without
+// voting) and cls_is_logits == 0 make the launches ssad_retinanet_detect_batch has always made
+int detect_batch_body(
     const float* const* cls_prob_host, const float* const* box_pred_host,
     const double* cell_anchors, int N, int levels, int A, int C, int k_min, const int* H_host,
     const int* W_host, float inference_th, int pre_nms_topn, int candidate_cap, float nms_thresh,
     int dets_per_im, const float* im_scale_host, const int* im_height_host, const int* im_width_host,
     float bbox_xform_clip, int class_specific, float* dets_out, int* counts_out, int* overflow_out,
-    void* workspace, size_t workspace_bytes, ssad_stream_t stream) {
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream, const ssad_detect_post* post, int cls_is_logits) {
   BPlan pl;
   BGeom g;
   const int rc = batch_plan(N, levels, A, C, H_host, W_host, pre_nms_topn, candidate_cap, &pl, g.E);
   if (rc) return rc;
   if (!cls_prob_host || !box_pred_host || !cell_anchors || !im_scale_host || !im_height_host || !im_width_host ||
       !dets_out || !counts_out || !overflow_out || dets_per_im < 1 || dets_per_im > pl.n ||
-      (class_specific != 0 && class_specific != 1))
+      (class_specific != 0 && class_specific != 1) || check_post(post) || (cls_is_logits != 0 && cls_is_logits != 1) ||
+      (cls_is_logits && !logit_classes_ok(C)))
     return SSAD_E_BADARG;
+  if (post_is_plain(post)) post = nullptr;
   BImages im;
   for (int i = 0; i < SSAD_DETECT_BATCH_MAX_IMAGES; ++i) {
     if (i < N && !(im_scale_host[i] > 0.0f)) return SSAD_E_BADARG;
@@ -296,7 +352,7 @@ int ssad_retinanet_detect_batch(
   }
   for (int l = 0; l < levels; ++l)
     if (!cls_prob_host[l] || !box_pred_host[l]) return SSAD_E_BADARG;
-  if (!workspace || workspace_bytes < batch_bytes(pl)) return SSAD_E_WORKSPACE;
+  if (!workspace || workspace_bytes < batch_bytes(pl) + (post ? batch_post_bytes(N, pl) : 0)) return SSAD_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   int blocks = 0;
   for (int l = 0; l < SSAD_MAX_LEVELS; ++l) {
@@ -306,8 +362,11 @@ int ssad_retinanet_detect_batch(
     g.W[l] = l < levels ? W_host[l] : 0;
     if (l >= levels) g.E[l] = 0;
     g.bstart[l] = blocks;
-    // one workgroup per kT * kCandIters float4 (an empty level gets none)
-    long long b = ((long long)g.E[l] + (long long)kT * 4 * kCandIters - 1) / ((long long)kT * 4 * kCandIters);
+    long long b;
+    if (cls_is_logits)     // one workgroup per (anchor, chunk of kT cells) item (an empty level gets none)
+      b = (long long)A * (((long long)g.H[l] * g.W[l] + kT - 1) / kT);
+    else                   // one workgroup per kT * kCandIters float4
+      b = ((long long)g.E[l] + (long long)kT * 4 * kCandIters - 1) / ((long long)kT * 4 * kCandIters);
     if (b > kCandMaxBlocks) b = kCandMaxBlocks;
     blocks += (int)b;
   }
@@ -335,11 +394,24 @@ int ssad_retinanet_detect_batch(
   unsigned long long* mask = (unsigned long long*)take(pl.slots * 2 * (size_t)pl.words);
   unsigned long long* fkeys = (unsigned long long*)take(pl.slots * 2);
   unsigned long long* fkeys_s = (unsigned long long*)take(pl.slots * 2);
+  int* pick_rank = nullptr;
+  unsigned* live = nullptr;
+  float* voted = nullptr;
+  if (post) {
+    pick_rank = (int*)take(pl.slots);
+    live = (unsigned*)take(pl.slots);
+    voted = (float*)take(pl.slots * 4);
+  }
 
   (void)hipMemsetAsync(counts, 0, pl.counts, s);                 // the call zeroes its own counters
   (void)hipMemsetAsync(overflow_out, 0, (size_t)N * 4, s);
-  if (blocks > 0)
-    hipLaunchKernelGGL(detb_candidates_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(kT), 0, s, g, counts, cand);
+  if (blocks > 0) {
+    if (cls_is_logits)
+      LAUNCH_BY_CLASSES(detb_candidates_logits_kernel, C + 1, dim3((unsigned)blocks, (unsigned)N), dim3(kT), 0, s, g,
+                        counts, cand);
+    else
+      hipLaunchKernelGGL(detb_candidates_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(kT), 0, s, g, counts, cand);
+  }
   hipLaunchKernelGGL(detb_topk_kernel, dim3((unsigned)levels, (unsigned)N), dim3(kTopT), (size_t)pre_nms_topn * 8, s,
                      counts, cand, candidate_cap, pre_nms_topn, keys_s, overflow_out);
   const unsigned nb = (unsigned)((pl.n + kT - 1) / kT), un = (unsigned)N;
@@ -347,16 +419,79 @@ int ssad_retinanet_detect_batch(
   hipLaunchKernelGGL(det_rank_sort_kernel, dim3(nb, un), dim3(kT), 0, s, ckeys, cvals, pl.n, 0, ckeys_s, cvals_s);
   hipLaunchKernelGGL(det_gather_kernel, dim3(nb, un), dim3(kT), 0, s, pl.n, ckeys_s, cvals_s, boxes, scores, sboxes,
                      sscores, scls);
-  hipLaunchKernelGGL(det_nms_mask_kernel, dim3(pl.words, pl.words, un), dim3(64), 0, s, pl.n, pl.words, sboxes, scls,
-                     nms_thresh, mask);
-  (void)hipMemsetAsync(fkeys, 0, pl.slots * 2, s);
-  hipLaunchKernelGGL(det_nms_scan_kernel, dim3((unsigned)C, un), dim3(kT), (size_t)pl.words * 8, s, pl.n, pl.words, C,
-                     scls, sscores, mask, fkeys);
+  if (!post || post->nms_method == SSAD_NMS_GREEDY) {
+    hipLaunchKernelGGL(det_nms_mask_kernel, dim3(pl.words, pl.words, un), dim3(64), 0, s, pl.n, pl.words, sboxes, scls,
+                       nms_thresh, mask);
+    (void)hipMemsetAsync(fkeys, 0, pl.slots * 2, s);
+    hipLaunchKernelGGL(det_nms_scan_kernel, dim3((unsigned)C, un), dim3(kT), (size_t)pl.words * 8, s, pl.n, pl.words, C,
+                       scls, sscores, mask, fkeys);
+  } else {
+    // Soft-NMS, one workgroup per (class, image): the same fkeys words (detect.hip's detect_body)
+    const int rs = ssad_soft_nms_images(sboxes, sscores, scls, pl.n, N, C, post->nms_method, post->sigma, nms_thresh,
+                                        post->score_thresh, fkeys, pick_rank, live, s);
+    if (rs) return rs;
+  }
+  const float* out_boxes = sboxes;
+  if (post && post->vote) {
+    // every survivor votes before the final sort; beta is 1 where it is no exponent, as ssad_box_voting passes it
+    const int m = post->scoring_method;
+    const bool exponent = m == SSAD_VOTE_TEMP_AVG || m == SSAD_VOTE_GENERALIZED_AVG || m == SSAD_VOTE_QUASI_SUM;
+    const int rv = ssad_box_voting_images(sboxes, scls, pl.n, sboxes, sscores, scls, pl.n, N, post->vote_thresh, m,
+                                          exponent ? post->beta : 1.0f, fkeys, voted, s);
+    if (rv) return rv;
+    out_boxes = voted;
+  }
   hipLaunchKernelGGL(det_rank_sort_kernel, dim3(nb, un), dim3(kT), 0, s, fkeys, (const int*)nullptr, pl.n, 1, fkeys_s,
                      (int*)nullptr);
   hipLaunchKernelGGL(det_emit_kernel, dim3((unsigned)((dets_per_im + kT - 1) / kT), un), dim3(kT), 0, s, pl.n,
-                     dets_per_im, fkeys_s, sboxes, scls, dets_out, counts_out);
+                     dets_per_im, fkeys_s, out_boxes, scls, dets_out, counts_out);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ssad_retinanet_detect_batch_workspace_bytes(int N, int levels, int A, int C, const int* H_host,
+                                                   const int* W_host, int pre_nms_topn, int candidate_cap) {
+  BPlan p;
+  if (batch_plan(N, levels, A, C, H_host, W_host, pre_nms_topn, candidate_cap, &p, nullptr)) return 0;
+  return batch_bytes(p);
+}
+
+int ssad_retinanet_detect_batch(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int N, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, int candidate_cap, float nms_thresh,
+    int dets_per_im, const float* im_scale_host, const int* im_height_host, const int* im_width_host,
+    float bbox_xform_clip, int class_specific, float* dets_out, int* counts_out, int* overflow_out,
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream) {
+  return detect_batch_body(cls_prob_host, box_pred_host, cell_anchors, N, levels, A, C, k_min, H_host, W_host,
+                           inference_th, pre_nms_topn, candidate_cap, nms_thresh, dets_per_im, im_scale_host,
+                           im_height_host, im_width_host, bbox_xform_clip, class_specific, dets_out, counts_out,
+                           overflow_out, workspace, workspace_bytes, stream, nullptr, 0);
+}
+
+size_t ssad_retinanet_detect_batch_ex_workspace_bytes(int N, int levels, int A, int C, const int* H_host,
+                                                      const int* W_host, int pre_nms_topn, int candidate_cap,
+                                                      const ssad_detect_post* post) {
+  BPlan p;
+  if (batch_plan(N, levels, A, C, H_host, W_host, pre_nms_topn, candidate_cap, &p, nullptr) || check_post(post))
+    return 0;
+  return batch_bytes(p) + (post_is_plain(post) ? 0 : batch_post_bytes(N, p));
+}
+
+int ssad_retinanet_detect_batch_ex(
+    const float* const* cls_prob_host, const float* const* box_pred_host,
+    const double* cell_anchors, int N, int levels, int A, int C, int k_min, const int* H_host,
+    const int* W_host, float inference_th, int pre_nms_topn, int candidate_cap, float nms_thresh,
+    int dets_per_im, const float* im_scale_host, const int* im_height_host, const int* im_width_host,
+    float bbox_xform_clip, int class_specific, float* dets_out, int* counts_out, int* overflow_out,
+    void* workspace, size_t workspace_bytes, ssad_stream_t stream, const ssad_detect_post* post, int cls_is_logits) {
+  return detect_batch_body(cls_prob_host, box_pred_host, cell_anchors, N, levels, A, C, k_min, H_host, W_host,
+                           inference_th, pre_nms_topn, candidate_cap, nms_thresh, dets_per_im, im_scale_host,
+                           im_height_host, im_width_host, bbox_xform_clip, class_specific, dets_out, counts_out,
+                           overflow_out, workspace, workspace_bytes, stream, post, cls_is_logits);
 }
 
 int ssad_detections_to_gt(const float* dets, const int* counts, const float* im_scale, int N, int dets_per_im,

@@ -8,11 +8,35 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ssad_kernels.h"
+
 namespace {
 
 constexpr int kT = 256;
 
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// what the post-processing options add behind the greedy path's workspace, per image of n slots: pick ranks,
+// Soft-NMS's own workspace, the voted boxes
+size_t post_bytes(size_t n) { return al(n * 4) + al(ssad_soft_nms_workspace_bytes((int)n)) + al(n * 16); }
+
+bool post_is_plain(const ssad_detect_post* post) {
+  return !post || (post->nms_method == SSAD_NMS_GREEDY && !post->vote);
+}
+
+int check_post(const ssad_detect_post* post) {
+  if (!post) return 0;
+  if (post->nms_method < SSAD_NMS_GREEDY || post->nms_method > SSAD_NMS_SOFT_GAUSSIAN) return SSAD_E_BADARG;
+  if (post->nms_method != SSAD_NMS_GREEDY && !(post->sigma > 0.0f)) return SSAD_E_BADARG;
+  if (post->vote) {
+    const int m = post->scoring_method;
+    if (m < SSAD_VOTE_ID || m > SSAD_VOTE_QUASI_SUM) return SSAD_E_BADARG;
+    if ((m == SSAD_VOTE_TEMP_AVG || m == SSAD_VOTE_GENERALIZED_AVG || m == SSAD_VOTE_QUASI_SUM) &&
+        !(post->beta > 0.0f))
+      return SSAD_E_BADARG;
+  }
+  return 0;
+}
 
 // Rank sort of `segs` segments of seg_len keys each (blockIdx.y = segment): out[rank] = key, rank = the number of keys
 // that precede it (descending: larger first; ascending: smaller first; equal keys in index order -- stable).  vals

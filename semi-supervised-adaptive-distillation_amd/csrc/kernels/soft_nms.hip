@@ -13,12 +13,16 @@
 // bookkeeping (see include/ssad_kernels.h); it is the reference's result whenever no two current scores tie at a
 // pick, and among equal scores the lower position goes first.  Worst case -- all n candidates in one class, none
 // retired -- the walk is n serial picks of n / 256 candidates a thread.
+//
+// Both kernels take the image from the grid (blockIdx.y) and address every per-image array as base + image * n, so
+// a minibatch's classes share one launch (detect_batch.hip); the single-image entries launch one image.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "ssad_kernels.h"
+#include "soft_nms_images.h"
 
 // The scores must come out as the reference's float32 arithmetic rounds them, one operation at a time.  hipcc
 // contracts a * b + c into an FMA by default, and the __fmul_rn / __fadd_rn of the HIP headers do not stop it (their
@@ -141,6 +145,10 @@ __device__ __forceinline__ void soft_nms_walk(const float* bx, unsigned* sc, int
 __global__ __launch_bounds__(kT) void soft_nms_kernel(int n, const float* boxes, const float* scores, const int* cls,
                                                       int method, float sigma, float nt, float thresh, u64* keys,
                                                       int* rank_out, unsigned* live) {
+  {
+    const long long im = (long long)blockIdx.y * n;             // this image's arrays
+    boxes += im * 4; scores += im; cls += im; keys += im; rank_out += im; live += im;
+  }
   __shared__ float lbox[kCap * 4];
   __shared__ unsigned lsc[kCap];
   __shared__ u64 wmax[2][kWaves];
@@ -168,13 +176,18 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// one wave per top detection
+// one wave per top detection; blockIdx.y = image
 __global__ __launch_bounds__(64) void box_voting_kernel(int m, const float* top_boxes, const int* top_cls,
                                                         const float* boxes, const float* scores, const int* cls, int n,
                                                         float vote_thresh, int scoring, float beta, u64* keys,
                                                         float* voted) {
   const int k = blockIdx.x;
   if (k >= m) return;
+  {
+    const long long tm = (long long)blockIdx.y * m, im = (long long)blockIdx.y * n;
+    top_boxes += tm * 4; top_cls += tm; keys += tm; voted += tm * 4;
+    boxes += im * 4; scores += im; cls += im;
+  }
   const u64 key = keys[k];
   const int c = top_cls[k];
   if (key == 0 || c < 0) return;                              // uniform
@@ -241,6 +254,25 @@ size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
+int ssad_soft_nms_images(const float* boxes, const float* scores, const int* cls, int n, int images, int C, int method,
+                         float sigma, float Nt, float score_thresh, unsigned long long* keys_out, int* pick_rank_out,
+                         unsigned* live, hipStream_t s) {
+  // the empty trailing slots belong to no class: no workgroup writes them
+  (void)hipMemsetAsync(keys_out, 0, (size_t)images * n * 8, s);
+  (void)hipMemsetAsync(pick_rank_out, 0xff, (size_t)images * n * 4, s);
+  hipLaunchKernelGGL(soft_nms_kernel, dim3((unsigned)C, (unsigned)images), dim3(kT), 0, s, n, boxes, scores, cls,
+                     method, sigma, Nt, score_thresh, keys_out, pick_rank_out, live);
+  return (int)hipGetLastError();
+}
+
+int ssad_box_voting_images(const float* top_boxes, const int* top_cls, int m, const float* boxes, const float* scores,
+                           const int* cls, int n, int images, float vote_thresh, int scoring_method, float beta,
+                           unsigned long long* keys_inout, float* voted_boxes_out, hipStream_t s) {
+  hipLaunchKernelGGL(box_voting_kernel, dim3((unsigned)m, (unsigned)images), dim3(64), 0, s, m, top_boxes, top_cls,
+                     boxes, scores, cls, n, vote_thresh, scoring_method, beta, keys_inout, voted_boxes_out);
+  return (int)hipGetLastError();
+}
+
 extern "C" {
 
 size_t ssad_soft_nms_workspace_bytes(int n) { return n > 0 ? al((size_t)n * 4) : 0; }
@@ -253,13 +285,8 @@ int ssad_soft_nms(const float* boxes, const float* scores, const int* cls, int n
   if (n == 0) return 0;
   if (!boxes || !scores || !cls || !keys_out || !pick_rank_out) return SSAD_E_BADARG;
   if (!workspace || workspace_bytes < ssad_soft_nms_workspace_bytes(n)) return SSAD_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  // the empty trailing slots belong to no class: no workgroup writes them
-  (void)hipMemsetAsync(keys_out, 0, (size_t)n * 8, s);
-  (void)hipMemsetAsync(pick_rank_out, 0xff, (size_t)n * 4, s);
-  hipLaunchKernelGGL(soft_nms_kernel, dim3(C), dim3(kT), 0, s, n, boxes, scores, cls, method, sigma, Nt, score_thresh,
-                     keys_out, pick_rank_out, (unsigned*)workspace);
-  return (int)hipGetLastError();
+  return ssad_soft_nms_images(boxes, scores, cls, n, 1, C, method, sigma, Nt, score_thresh, keys_out, pick_rank_out,
+                              (unsigned*)workspace, (hipStream_t)stream);
 }
 
 int ssad_box_voting(const float* top_boxes, const int* top_cls, int m, const float* boxes, const float* scores,
@@ -273,9 +300,8 @@ int ssad_box_voting(const float* top_boxes, const int* top_cls, int m, const flo
   if (m == 0) return 0;
   if (!top_boxes || !top_cls || !keys_inout || !voted_boxes_out || (n > 0 && (!boxes || !scores || !cls)))
     return SSAD_E_BADARG;
-  hipLaunchKernelGGL(box_voting_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, m, top_boxes, top_cls, boxes,
-                     scores, cls, n, vote_thresh, scoring_method, exponent ? beta : 1.0f, keys_inout, voted_boxes_out);
-  return (int)hipGetLastError();
+  return ssad_box_voting_images(top_boxes, top_cls, m, boxes, scores, cls, n, 1, vote_thresh, scoring_method,
+                                exponent ? beta : 1.0f, keys_inout, voted_boxes_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

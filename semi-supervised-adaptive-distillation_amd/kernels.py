@@ -306,6 +306,10 @@ def lib():
     L.ssad_retinanet_detect_batch_workspace_bytes.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32]
     L.ssad_retinanet_detect_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, i32, i32, f32, i32,
                                               vp, vp, vp, f32, i32, vp, vp, vp, vp, sz, vp]
+    L.ssad_retinanet_detect_batch_ex_workspace_bytes.restype = sz
+    L.ssad_retinanet_detect_batch_ex_workspace_bytes.argtypes = [i32, i32, i32, i32, vp, vp, i32, i32,
+                                                                 C.POINTER(DetectPost)]
+    L.ssad_retinanet_detect_batch_ex.argtypes = L.ssad_retinanet_detect_batch.argtypes + [C.POINTER(DetectPost), i32]
     L.ssad_detections_to_gt.argtypes = [vp, vp, vp, i32, i32, f32, i32, vp, vp, vp, vp]
     L.ssad_kernels_arch.restype = C.c_char_p
     L.ssad_kernels_abi_version.restype = i32

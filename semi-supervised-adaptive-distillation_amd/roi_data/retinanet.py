@@ -234,7 +234,7 @@ class RetinanetDetector(object):
 
 class BatchedRetinanetDetector(object):
     """`RetinanetDetector` for a minibatch: N images per call, one kernel sequence whose length does not depend on N
-    (ssad_retinanet_detect_batch), no Soft-NMS / voting / softmax options.
+    (ssad_retinanet_detect_batch / ssad_retinanet_detect_batch_ex).
 
     `__call__(cls_probs, box_preds, im_heights, im_widths, im_scales)` takes the per-level sigmoid scores
     [N][A*C][H][W] and box deltas [N][A*4][H][W] ([N][A*4*C][H][W] with `class_specific_bbox=True`) as device tensors
@@ -242,6 +242,14 @@ class BatchedRetinanetDetector(object):
     (dets float32 [N][dets_per_im][6], counts int32 [N]): image n's rows are dets[n, :counts[n]], bit for bit the rows
     RetinanetDetector gives on the [n:n+1] slices; rows from counts[n] on are zero.  Both tensors are this object's
     buffers: the next call overwrites them.
+
+    `soft_nms`, `bbox_vote` and `softmax` mean what they mean to RetinanetDetector and are checked the same way:
+    Soft-NMS and box voting run for all N images in one launch each.  `softmax=True` takes the foreground
+    probabilities [N][A*C][H][W], or, with `__call__(..., from_logits=True)`, the softmax head's cls_pred logits
+    [N][A*(C+1)][H][W] (DistillHeads' cls_logits), which one group_spatial_softmax(drop_background=True) launch per
+    level turns into the former for the whole batch, in buffers allocated here.  (ssad_retinanet_detect_batch_ex can
+    read the logits itself, cls_is_logits = 1; measured, that fused pass was not faster than this route --
+    profiles/detect_batch.md; `fused_logits=True` selects it, and then no probability buffer is allocated.)
 
     Only scores above the threshold become sort keys, in lists of `candidate_capacity` keys per (image, level).  An
     image with a fuller level is reported by the kernels; `__call__` reads those N flags (the one device-to-host copy
@@ -258,7 +266,14 @@ class BatchedRetinanetDetector(object):
 
     def __init__(self, N, level_shapes, cfg=AnchorConfig, inference_th=0.05, pre_nms_topn=1000,
                  nms_thresh=0.5, dets_per_im=100, device="cuda", *, class_specific_bbox=False,
-                 candidate_capacity=None):
+                 candidate_capacity=None, soft_nms=None, bbox_vote=None, softmax=False,
+                 fused_logits=False):
+        self.post = RetinanetDetector._post(soft_nms, bbox_vote)
+        self.softmax = RetinanetDetector._softmax_args(softmax, False)
+        self._options = dict(soft_nms=soft_nms, bbox_vote=bbox_vote, softmax=self.softmax)
+        if not isinstance(fused_logits, (bool, np.bool_)):
+            raise K.KernelError("fused_logits= is a boolean")
+        self.fused_logits = bool(fused_logits)
         if not isinstance(class_specific_bbox, (bool, np.bool_)):
             raise K.KernelError("class_specific_bbox= is a boolean")
         self.class_specific_bbox = bool(class_specific_bbox)
@@ -279,8 +294,13 @@ class BatchedRetinanetDetector(object):
         IntArr = C.c_int * self.levels
         self._H = IntArr(*[h for h, _ in self.shapes])
         self._W = IntArr(*[w for _, w in self.shapes])
-        nb = K.lib().ssad_retinanet_detect_batch_workspace_bytes(self.N, self.levels, self.A, self.C, self._H,
-                                                                 self._W, self.topn, self.capacity)
+        if self.post is None:
+            nb = K.lib().ssad_retinanet_detect_batch_workspace_bytes(self.N, self.levels, self.A, self.C, self._H,
+                                                                     self._W, self.topn, self.capacity)
+        else:
+            nb = K.lib().ssad_retinanet_detect_batch_ex_workspace_bytes(self.N, self.levels, self.A, self.C, self._H,
+                                                                        self._W, self.topn, self.capacity,
+                                                                        C.byref(self.post))
         if nb == 0:
             raise K.KernelError("retinanet_detect_batch: unsupported geometry")
         self.cells = torch.as_tensor(cell_anchors(cfg)[:self.levels], dtype=torch.float64,
@@ -289,16 +309,23 @@ class BatchedRetinanetDetector(object):
         self.out = torch.zeros((self.N, self.keep, 6), dtype=torch.float32, device=device)
         self.counts = torch.zeros(self.N, dtype=torch.int32, device=device)
         self.overflow = torch.zeros(self.N, dtype=torch.int32, device=device)
+        # from_logits=True: the batch's foreground probabilities (group_spatial_softmax writes them, the candidate
+        # pass reads them: the fused pass of ssad_retinanet_detect_batch_ex was not faster, profiles/detect_batch.md)
+        self._probs = [torch.empty((self.N, self.A * self.C, h, w), dtype=torch.float32, device=device)
+                       for h, w in self.shapes] if self.softmax and not self.fused_logits else None
         self.last_fallback = []
         self._single = None
 
-    def _check_inputs(self, cls_probs, box_preds, im_heights, im_widths, im_scales):
+    def _check_inputs(self, cls_probs, box_preds, im_heights, im_widths, im_scales, from_logits=False):
         if len(cls_probs) != self.levels or len(box_preds) != self.levels:
             raise K.KernelError("one cls_prob and one box_pred tensor per level (%d)" % self.levels)
         box_ch = self.A * 4 * (self.C if self.class_specific_bbox else 1)
+        cls_ch = self.A * (self.C + 1 if from_logits else self.C)
         for t, (h, w) in zip(cls_probs, self.shapes):
-            if tuple(t.shape) != (self.N, self.A * self.C, h, w) or t.dtype != torch.float32 or \
+            if tuple(t.shape) != (self.N, cls_ch, h, w) or t.dtype != torch.float32 or \
                     not t.is_contiguous() or not t.is_cuda:
+                if from_logits:
+                    raise K.KernelError("cls_pred logits must be N x A*(C+1) x H x W contiguous float32 device tensors")
                 raise K.KernelError("cls_prob must be N x A*C x H x W contiguous float32 device tensors")
         for t, (h, w) in zip(box_preds, self.shapes):
             if tuple(t.shape) != (self.N, box_ch, h, w) or t.dtype != torch.float32 or \
@@ -310,27 +337,39 @@ class BatchedRetinanetDetector(object):
         if not all(float(s) > 0 for s in im_scales):
             raise K.KernelError("every im_scale must be positive")
 
-    def __call__(self, cls_probs, box_preds, im_heights, im_widths, im_scales):
-        self._check_inputs(cls_probs, box_preds, im_heights, im_widths, im_scales)
+    def __call__(self, cls_probs, box_preds, im_heights, im_widths, im_scales, *, from_logits=False):
+        RetinanetDetector._softmax_args(self.softmax, from_logits)
+        self._check_inputs(cls_probs, box_preds, im_heights, im_widths, im_scales, from_logits)
         PtrArr = C.c_void_p * self.levels
-        rc = K.lib().ssad_retinanet_detect_batch(
-            PtrArr(*[t.data_ptr() for t in cls_probs]), PtrArr(*[t.data_ptr() for t in box_preds]),
+        scores = cls_probs
+        if from_logits and not self.fused_logits:
+            scores = [K.group_spatial_softmax(t, self.C + 1, drop_background=True, out=o)
+                      for t, o in zip(cls_probs, self._probs)]
+        args = (
+            PtrArr(*[t.data_ptr() for t in scores]), PtrArr(*[t.data_ptr() for t in box_preds]),
             C.c_void_p(self.cells.data_ptr()), self.N, self.levels, self.A, self.C, self.cfg.k_min, self._H, self._W,
             self.th, self.topn, self.capacity, self.nms, self.keep,
             (C.c_float * self.N)(*[float(s) for s in im_scales]), (C.c_int * self.N)(*[int(h) for h in im_heights]),
             (C.c_int * self.N)(*[int(w) for w in im_widths]), float(np.log(1000. / 16.)),
             int(self.class_specific_bbox), C.c_void_p(self.out.data_ptr()), C.c_void_p(self.counts.data_ptr()),
             C.c_void_p(self.overflow.data_ptr()), C.c_void_p(self.ws.data_ptr()), self.ws.numel(), K._stream())
+        fused = bool(from_logits and self.fused_logits)
+        if self.post is None and not fused:
+            rc = K.lib().ssad_retinanet_detect_batch(*args)
+        else:
+            rc = K.lib().ssad_retinanet_detect_batch_ex(
+                *args, C.byref(self.post) if self.post is not None else None, int(fused))
         if rc:
             raise K.KernelError("retinanet_detect_batch failed (%d)" % rc)
         self.last_fallback = [int(n) for n in torch.nonzero(self.overflow).flatten().cpu().numpy()]
         for n in self.last_fallback:
             if self._single is None:
                 self._single = RetinanetDetector(self.shapes, self.cfg, self.th, self.topn, self.nms, self.keep,
-                                                 self.device, class_specific_bbox=self.class_specific_bbox)
+                                                 self.device, class_specific_bbox=self.class_specific_bbox,
+                                                 **self._options)
             # slices of an [N][ch][H][W] tensor are contiguous; the detector's own buffers hold all dets_per_im rows
             self._single([t[n:n + 1] for t in cls_probs], [t[n:n + 1] for t in box_preds],
-                         im_heights[n], im_widths[n], im_scales[n])
+                         im_heights[n], im_widths[n], im_scales[n], from_logits=from_logits)
             self.out[n].copy_(self._single.out)
             self.counts[n:n + 1].copy_(self._single.count)
         return self.out, self.counts

@@ -13,7 +13,10 @@ Timing: wall clock around the call(s) between two device synchronisations -- bot
 of what a caller pays.  The two paths alternate; a warm-up, then the median of --iters rounds.  The rows of the two
 paths are compared bit for bit before anything is timed.  Prints one JSON line.
 
-    python tools/detect_batch_bench.py [--iters 30] [--warmup 3] [--share 0.001] [--commit ID] [--out profiles/detect_batch.md]"""
+    python tools/detect_batch_bench.py [--iters 30] [--warmup 3] [--share 0.001] [--commit ID] [--out profiles/detect_batch.md]
+
+With --softmax, or --soft-nms METHOD [--vote], it times the batched call with that option instead (options_main) and
+only prints its JSON line; profiles/detect_batch.md quotes those lines under "Options"."""
 import argparse
 import json
 import os
@@ -53,6 +56,86 @@ def traffic_bytes(cand_per_level, cap, topn=TOPN):
     return scores, scores + keys + topk + stages
 
 
+def alternate(torch, paths, iters, warmup):
+    """{label: fn} -> {label: [median, min, max] ms}: the paths take turns, wall clock between two synchronisations"""
+    for _ in range(warmup):
+        for fn in paths.values():
+            fn()
+    t = {label: [] for label in paths}
+    for _ in range(iters):
+        for label, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            t[label].append((time.perf_counter() - t0) * 1e3)
+    return {label: [float(np.median(v)), float(np.min(v)), float(np.max(v))] for label, v in t.items()}
+
+
+def same_rows(torch, dets, counts, rows_per_image, what):
+    for n, rows in enumerate(rows_per_image):
+        assert int(counts[n]) == rows.shape[0] and torch.equal(dets[n, :rows.shape[0]].view(torch.int32),
+                                                               rows.view(torch.int32)), (what, n)
+
+
+def options_main(args, torch):
+    """--softmax: the batched call on the softmax head's logits against (a) the loop of per-image from_logits calls
+    and (b) group_spatial_softmax(drop_background) on the whole batch + the batched call on probabilities.
+    --soft-nms METHOD [--vote]: the batched call with the option(s) against the per-image loop, on the sparse sigmoid
+    scores of the default mode.  Prints one JSON line; writes no file."""
+    from ssad_amd import kernels as K
+    from ssad_amd.roi_data.retinanet import BatchedRetinanetDetector, RetinanetDetector
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    rand = lambda *shape: torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32)
+    deltas = [torch.randn((N, 36, h, w), generator=gen, device="cuda") * 0.4 for h, w in SHAPES]
+    sizes = ([IM_H] * N, [IM_W] * N, [1.0] * N)
+    kw = {}
+    if args.soft_nms:
+        kw["soft_nms"] = dict(method=args.soft_nms)
+    if args.vote:
+        kw["bbox_vote"] = dict()
+    loop_of = lambda det, maps, **ckw: [det([p[n:n + 1] for p in maps], [d[n:n + 1] for d in deltas], IM_H, IM_W, 1.0,
+                                            **ckw).clone() for n in range(N)]
+    if args.softmax:
+        maps = []
+        for h, w in SHAPES:
+            x = torch.zeros((N, 9, 81, h, w), device="cuda")
+            x[:, :, 1:] = -9.0 + 2.0 * rand(N, 9, 80, h, w)
+            p = 0.06 + 0.84 * rand(N, 9, 80, h, w)
+            x[:, :, 1:] = torch.where(rand(N, 9, 80, h, w) < args.share, torch.log(p / (1.0 - p)), x[:, :, 1:])
+            maps.append(x.reshape(N, 9 * 81, h, w).contiguous())
+        batch = BatchedRetinanetDetector(N, SHAPES, softmax=True, **kw)
+        fused = BatchedRetinanetDetector(N, SHAPES, softmax=True, fused_logits=True, **kw)
+        single = RetinanetDetector(SHAPES, softmax=True, **kw)
+        bufs = [torch.empty((N, AC, h, w), device="cuda") for h, w in SHAPES]
+        two_pass = lambda: batch([K.group_spatial_softmax(x, 81, drop_background=True, out=o)
+                                  for x, o in zip(maps, bufs)], deltas, *sizes)
+        paths = {"fused": lambda: fused(maps, deltas, *sizes, from_logits=True),
+                 "softmax + batched": two_pass,
+                 "loop": lambda: loop_of(single, maps, from_logits=True)}
+        two_pass()
+        above = sum(int((b > 0.05).sum()) for b in bufs) / float(sum(b.numel() for b in bufs))
+    else:
+        maps = []
+        for h, w in SHAPES:
+            low, high = 0.001 + 0.039 * rand(N, AC, h, w), 0.05 + 0.95 * rand(N, AC, h, w)
+            maps.append(torch.where(rand(N, AC, h, w) < args.share, high, low).contiguous())
+        batch = BatchedRetinanetDetector(N, SHAPES, **kw)
+        single = RetinanetDetector(SHAPES, **kw)
+        paths = {"batched": lambda: batch(maps, deltas, *sizes), "loop": lambda: loop_of(single, maps)}
+        above = sum(int((p > 0.05).sum()) for p in maps) / float(sum(p.numel() for p in maps))
+    want = paths["loop"]()
+    for label, fn in paths.items():
+        if label != "loop":
+            dets, counts = fn()
+            assert batch.last_fallback == [] and (not args.softmax or fused.last_fallback == []), label
+            same_rows(torch, dets, counts, want, label)
+    results = alternate(torch, paths, args.iters, args.warmup)
+    print(json.dumps({"mode": "softmax" if args.softmax else "scores", "options": {k: dict(v) for k, v in kw.items()},
+                      "iters": args.iters, "commit": args.commit or commit_id(), "share_above_threshold": above,
+                      "rows_per_image": [int(r.shape[0]) for r in want][:4], "median_min_max_ms": results}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
@@ -60,12 +143,17 @@ def main():
     ap.add_argument("--share", type=float, default=0.001)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detect_batch.md"))
+    ap.add_argument("--softmax", action="store_true", help="time the batched call on softmax logits")
+    ap.add_argument("--soft-nms", default=None, choices=["hard", "linear", "gaussian"])
+    ap.add_argument("--vote", action="store_true", help="with --soft-nms / --softmax: add box voting")
     args = ap.parse_args()
     import torch
     import ssad_amd  # noqa: F401
     from ssad_amd.roi_data.retinanet import BatchedRetinanetDetector, RetinanetDetector
     if not torch.cuda.is_available():
         raise SystemExit("detect_batch_bench needs a GPU: nothing is estimated without one")
+    if args.softmax or args.soft_nms or args.vote:
+        return options_main(args, torch)
     gen = torch.Generator(device="cuda").manual_seed(0)
     rand = lambda *shape: torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32)
     deltas = [torch.randn((N, 36, h, w), generator=gen, device="cuda") * 0.4 for h, w in SHAPES]
@@ -153,8 +241,14 @@ def main():
         "",
         "This one same-process measurement is all the speed claim rests on; no ratio was fixed in advance.",
     ]
+    kept = ""                                      # the hand-written "Options" section survives a rewrite
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            old = f.read()
+        if "\n## Options" in old:
+            kept = old[old.index("\n## Options"):]
     with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        f.write("\n".join(lines) + "\n" + kept)
     print(json.dumps({"iters": args.iters, "commit": commit, "share_above_threshold": above,
                       "median_min_max_ms": results, "loop_over_batched_sparse": ratio,
                       "loop_over_batched_dense": ratio_dense, "bytes_per_image": moved, "floor_bytes": floor}))
