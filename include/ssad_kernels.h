@@ -697,6 +697,30 @@ SSAD_API int ssad_grouped_conv3x3_pack_filter(const float* w, int C, int group, 
 SSAD_API int ssad_grouped_conv3x3_forward(const float* x, const float* packed, const float* bias, int N, int C,
                                           int H, int W, int group, int stride, int relu, float* y,
                                           ssad_stream_t stream);
+/* The two gradients of that layer (grouped_conv3x3_grad.hip; conv_op_impl.h:451-500,524-560 per group), same
+ * geometry and widths; every entry returns SSAD_E_BADARG / -1 before any launch for another width, C % group != 0,
+ * a stride other than 1 or 2, non-positive sizes, a missing pointer or a grid past the launch limit.
+ * Data gradient: dx[n][g cg + c][iy][ix] = sum_m sum_(ky,kx) w[g cg + m][c][ky][kx] dy[n][g cg + m][oy][ox] over
+ * oy s + ky - 1 = iy, ox s + kx - 1 = ix; every element of dx [N][C][H][W] is written.  packed = the filter in the
+ * data gradient's operand order (per group transposed, taps flipped: the forward layout of that filter, so
+ * _dgrad_filter_floats == _filter_floats).  relu_x (or NULL) [N][C][H][W]: dx = 0 where relu_x <= 0.  H, W: the
+ * INPUT's; dy is [N][C][(H-1)/stride + 1][(W-1)/stride + 1]. */
+SSAD_API long long ssad_grouped_conv3x3_dgrad_filter_floats(int C, int group);
+SSAD_API int ssad_grouped_conv3x3_pack_filter_dgrad(const float* w, int C, int group, float* packed,
+                                                    ssad_stream_t stream);
+SSAD_API int ssad_grouped_conv3x3_dgrad(const float* dy, const float* packed, const float* relu_x, int N, int C,
+                                        int H, int W, int group, int stride, float* dx, ssad_stream_t stream);
+/* Filter gradient: dw[g cg + m][c][ky][kx] = sum_n sum_(oy,ox) dy[n][g cg + m][oy][ox] x[n][g cg + c][oy s + ky - 1]
+ * [ox s + kx - 1] (zero outside the image), overwritten.  No float atomics: the T = N ceil(OH / TR) ceil(OW / 16)
+ * pixel tiles (TR = 8 rows at stride 1, 4 at stride 2) are cut into SPLIT = min(T, max(1, 1024 / B)) contiguous
+ * ranges, B = group / GPW workgroups per range (GPW = 4, 4, 2, 1 groups at 4, 8, 16, 32 channels per group; at 64
+ * B = 4 group); range r writes partial r and a second launch adds the partials in the order r = 0, 1, ...
+ * _workspace_bytes = SPLIT * C * (C / group) * 9 * 4, 0 for a geometry the kernels refuse; a smaller workspace is
+ * SSAD_E_BADARG. */
+SSAD_API size_t ssad_grouped_conv3x3_wgrad_workspace_bytes(int N, int C, int H, int W, int group, int stride);
+SSAD_API int ssad_grouped_conv3x3_wgrad(const float* x, const float* dy, int N, int C, int H, int W, int group,
+                                        int stride, float* dw, void* workspace, size_t workspace_bytes,
+                                        ssad_stream_t stream);
 /* MaxPool / MaxPoolGradient, NCHW (caffe2/operators/pool_op.cu): windows are clipped to
  * the image; every input equal to its window's maximum receives the gradient */
 SSAD_API int ssad_max_pool_forward(const float* x, int N, int C, int H, int W, int kh, int kw,

@@ -47,6 +47,10 @@ bool ConvOp<float, HIPContext>::RunDefaultEngine();
 template <>
 bool ConvGradientOp<float, HIPContext>::RunDefaultEngine();
 template <>
+bool ConvOp<float, HIPContext>::RunGrouped();
+template <>
+bool ConvGradientOp<float, HIPContext>::RunGrouped();
+template <>
 bool ConvOp<float, HIPContext>::RunFloat16();
 template <>
 bool ConvOp<float, HIPContext>::RunFloat16Pointwise();
@@ -59,6 +63,25 @@ namespace {
 size_t BlockedHalves(int N, int C, int H, int W) {
   return (size_t)N * (size_t)((C + 7) / 8) * 8 * (size_t)H * (size_t)W;
 }
+
+// hip_algo = "grouped" is a request, not a hint: the geometry of kernels/grouped_conv3x3.hip / grouped_conv3x3_grad.hip
+// or a failure that names the operator and the geometry -- never the default engine behind the caller's back.
+string GroupedGeometryText(const ConvGeometry& g, int N, int C, int M, int H, int W) {
+  std::ostringstream o;
+  o << "kernel " << g.kernel[0] << "x" << g.kernel[1] << ", stride " << g.stride[0] << "x" << g.stride[1] << ", pads "
+    << g.pads[0] << "," << g.pads[1] << "," << g.pads[2] << "," << g.pads[3] << ", dilation " << g.dilation[0] << "x"
+    << g.dilation[1] << ", group " << g.group << ", " << C << " -> " << M << " channels, N " << N << ", " << H << "x" << W;
+  return o.str();
+}
+void EnforceGroupedGeometry(const char* op, const ConvGeometry& g, int N, int C, int M, int H, int W) {
+  const int cg = (g.group > 0 && C % g.group == 0) ? C / g.group : 0;
+  const bool ok = g.kernel == vector<int>{3, 3} && g.pads == vector<int>{1, 1, 1, 1} && g.dilation == vector<int>{1, 1} &&
+                  g.stride[0] == g.stride[1] && (g.stride[0] == 1 || g.stride[0] == 2) && M == C &&
+                  (cg == 4 || cg == 8 || cg == 16 || cg == 32 || cg == 64) && N >= 1 && H >= 1 && W >= 1;
+  CAFFE_ENFORCE(ok, op, "(hip_algo=grouped): ", GroupedGeometryText(g, N, C, M, H, W),
+                " -- the grouped engine takes kernel 3x3, pad 1, stride 1 or 2, dilation 1 and 4, 8, 16, 32 or 64 "
+                "input = output channels per group");
+}
 }  // namespace
 
 template <>
@@ -66,6 +89,9 @@ bool ConvOp<float, HIPContext>::RunOnDevice() {
   auto& X = Input(INPUT);
   auto& filter = Input(FILTER);
   auto* Y = Output(0);
+  CAFFE_ENFORCE(!(algo_ == "grouped" && fuse_sigmoid_),
+                "Conv(hip_algo=grouped): fuse_sigmoid is not an epilogue of the grouped engine");
+  CAFFE_ENFORCE(!(algo_ == "grouped" && X.IsType<float16>()), "Conv(hip_algo=grouped): fp32 blobs only");
   CAFFE_ENFORCE(!fuse_sigmoid_ || (!X.IsType<float16>() && IsSubnetGeometry(geom_)),
                 "Conv(fuse_sigmoid): only the fp32 3x3 / stride 1 / pad 1 engines carry the Sigmoid epilogue");
   if (X.IsType<float16>()) return RunFloat16();
@@ -84,6 +110,7 @@ bool ConvOp<float, HIPContext>::RunOnDevice() {
     CAFFE_ENFORCE(b.dim32(0) == M);
     bias = b.data<float>();
   }
+  if (algo_ == "grouped") return RunGrouped();
   if (!IsSubnetGeometry(geom_)) return RunDefaultEngine();
   Y->Resize(N, M, H, W);   // 3x3 / s1 / p1 keeps the spatial size
 
@@ -110,6 +137,77 @@ bool ConvOp<float, HIPContext>::RunOnDevice() {
               : ssad_conv3x3_forward(&lv, 1, packed, bias, M, C, flags, s);
   CAFFE_ENFORCE_EQ(rc, 0, "Conv launch failed");
   ++g_conv_launch_calls;
+  return true;
+}
+
+// hip_algo = "grouped", forward: ssad_grouped_conv3x3_forward on the cached pack of the filter.
+template <>
+bool ConvOp<float, HIPContext>::RunGrouped() {
+  auto& X = Input(INPUT);
+  auto& filter = Input(FILTER);
+  auto* Y = Output(0);
+  const int N = X.dim32(0), C = X.dim32(1), H = X.dim32(2), W = X.dim32(3);
+  const int M = filter.dim32(0);
+  EnforceGroupedGeometry("Conv", geom_, N, C, M, H, W);
+  const int st = geom_.stride[0];
+  Y->Resize(N, M, (H - 1) / st + 1, (W - 1) / st + 1);
+  hipStream_t s = context_.hip_stream();
+  const long long before = pack_cache_.packs_issued();
+  pack_cache_.Want(filter, FilterPackCache::GROUPED_FWD);
+  pack_cache_.Flush(s);
+  g_filter_packs_issued += pack_cache_.packs_issued() - before;
+  const int rc = ssad_grouped_conv3x3_forward(X.data<float>(), pack_cache_.Packed(filter, FilterPackCache::GROUPED_FWD),
+                                              InputSize() == 3 ? Input(BIAS).data<float>() : nullptr, N, C, H, W,
+                                              geom_.group, st, fuse_relu_ ? 1 : 0, Y->mutable_data<float>(), s);
+  CAFFE_ENFORCE_EQ(rc, 0, "Conv(hip_algo=grouped) launch failed: ", GroupedGeometryText(geom_, N, C, M, H, W));
+  ++g_conv_launch_calls;
+  return true;
+}
+
+// hip_algo = "grouped", backward: dfilter from ssad_grouped_conv3x3_wgrad (per-range partials in the operator's
+// workspace, added in a fixed order), dX from ssad_grouped_conv3x3_dgrad with the ReluGradient of the layer below as
+// its mask operand, dbias as on the default engine.
+template <>
+bool ConvGradientOp<float, HIPContext>::RunGrouped() {
+  auto& X = Input(INPUT);
+  auto& filter = Input(FILTER);
+  auto& dY = Input(OUTPUT_GRAD);
+  auto* dfilter = Output(FILTER_GRAD);
+  const int N = X.dim32(0), C = X.dim32(1), H = X.dim32(2), W = X.dim32(3);
+  const int M = filter.dim32(0);
+  EnforceGroupedGeometry("ConvGradient", geom_, N, C, M, H, W);
+  const int st = geom_.stride[0], OH = (H - 1) / st + 1, OW = (W - 1) / st + 1;
+  CAFFE_ENFORCE(dY.dim32(0) == N && dY.dim32(1) == M && dY.dim32(2) == OH && dY.dim32(3) == OW,
+                "output gradient shape does not match the convolution output");
+  dfilter->ResizeLike(filter);
+  hipStream_t s = context_.hip_stream();
+  const size_t wsb = ssad_grouped_conv3x3_wgrad_workspace_bytes(N, C, H, W, geom_.group, st);
+  CAFFE_ENFORCE(wsb > 0, "ConvGradient(hip_algo=grouped): ", GroupedGeometryText(geom_, N, C, M, H, W));
+  workspace_.Resize((TIndex)wsb);
+  int rc = ssad_grouped_conv3x3_wgrad(X.data<float>(), dY.data<float>(), N, C, H, W, geom_.group, st,
+                                      dfilter->mutable_data<float>(), workspace_.mutable_data<uint8_t>(), wsb, s);
+  CAFFE_ENFORCE_EQ(rc, 0, "ConvGradient(hip_algo=grouped) filter launch failed: ",
+                   GroupedGeometryText(geom_, N, C, M, H, W));
+  ++g_conv_launch_calls;
+  if (!no_bias_) {
+    auto* dbias = Output(BIAS_OR_INPUT_GRAD);
+    dbias->Resize(M);
+    CAFFE_ENFORCE_EQ(ssad_channel_sum(dY.data<float>(), N, M, OH * OW, dbias->mutable_data<float>(), 0, s), 0);
+  }
+  if (OutputSize() == 3 || (no_bias_ && OutputSize() == 2)) {
+    auto* dX = Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD);
+    dX->ResizeLike(X);
+    const long long before = pack_cache_.packs_issued();
+    pack_cache_.Want(filter, FilterPackCache::GROUPED_DGRAD);
+    pack_cache_.Flush(s);
+    g_filter_packs_issued += pack_cache_.packs_issued() - before;
+    rc = ssad_grouped_conv3x3_dgrad(dY.data<float>(), pack_cache_.Packed(filter, FilterPackCache::GROUPED_DGRAD),
+                                    relu_grad_on_input_ ? X.data<float>() : nullptr, N, C, H, W, geom_.group, st,
+                                    dX->mutable_data<float>(), s);
+    CAFFE_ENFORCE_EQ(rc, 0, "ConvGradient(hip_algo=grouped) data launch failed: ",
+                     GroupedGeometryText(geom_, N, C, M, H, W));
+    ++g_conv_launch_calls;
+  }
   return true;
 }
 
@@ -399,6 +497,7 @@ bool ConvGradientOp<float, HIPContext>::RunOnDevice() {
   auto& filter = Input(FILTER);
   auto& dY = Input(OUTPUT_GRAD);
   auto* dfilter = Output(FILTER_GRAD);
+  CAFFE_ENFORCE(!(algo_ == "grouped" && X.IsType<float16>()), "ConvGradient(hip_algo=grouped): fp32 blobs only");
   if (X.IsType<float16>()) return RunFloat16();
   CAFFE_ENFORCE_EQ(X.ndim(), 4);
   CAFFE_ENFORCE_EQ(X.ndim(), filter.ndim());
@@ -407,6 +506,7 @@ bool ConvGradientOp<float, HIPContext>::RunOnDevice() {
   CAFFE_ENFORCE(filter.dim32(1) * geom_.group == C);
   CAFFE_ENFORCE(filter.dim32(2) == geom_.kernel[0] && filter.dim32(3) == geom_.kernel[1]);
   CAFFE_ENFORCE_EQ(dY.ndim(), 4);
+  if (algo_ == "grouped") return RunGrouped();
   if (!IsSubnetGeometry(geom_)) return RunDefaultEngine();
   CAFFE_ENFORCE(dY.dim32(0) == N && dY.dim32(1) == M && dY.dim32(2) == H && dY.dim32(3) == W,
                 "output gradient shape does not match the convolution output");

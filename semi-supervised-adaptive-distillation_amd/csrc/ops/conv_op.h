@@ -32,6 +32,9 @@
 //   ConvGradient  relu_grad_on_input=1    dX masked by X > 0 (= ReluGradient of
 //                                         the in-place Relu that produced X)
 //   both          hip_algo="direct"|"winograd"   pin the algorithm (default: by width)
+//   both          hip_algo="grouped"      opt-in: a grouped 3x3 / pad 1 / stride 1|2 layer with 4, 8, 16, 32 or 64
+//                                         channels per group (ResNeXt) on kernels/grouped_conv3x3{,_grad}.hip instead
+//                                         of the default engine; any other geometry fails by name (no fall-back)
 #ifndef C2HIP_CONV_OP_H_
 #define C2HIP_CONV_OP_H_
 
@@ -162,6 +165,7 @@ class ConvOp final : public Operator<Context> {
 
  private:
   bool RunDefaultEngine();
+  bool RunGrouped();
   bool RunFloat16();
   ConvGeometry geom_;
   int fuse_relu_;
@@ -199,6 +203,7 @@ class ConvGradientOp final : public Operator<Context> {
   int relu_grad_on_input_;
   string algo_;
   bool RunDefaultEngine();
+  bool RunGrouped();
   bool RunFloat16();
   Tensor<Context> packed_filter_;
   FilterPackCache pack_cache_;

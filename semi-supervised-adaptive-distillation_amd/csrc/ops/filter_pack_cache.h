@@ -19,7 +19,8 @@ namespace caffe2 {
 class FilterPackCache {
  public:
   enum Kind { WINO_FWD = 0, WINO_DGRAD = 1, DIRECT_FWD = 2, DIRECT_DGRAD = 3, WINO24_FWD = 4, WINO24_DGRAD = 5,
-              SPLIT_FWD = 6, SPLIT_DGRAD = 7 };     // 6 / 7: the split-operand engine's packs (conv3x3_split.hip)
+              SPLIT_FWD = 6, SPLIT_DGRAD = 7,       // 6 / 7: the split-operand engine's packs (conv3x3_split.hip)
+              GROUPED_FWD = 8, GROUPED_DGRAD = 9 }; // hip_algo = "grouped": filter [C][C/group][3][3], group = M / C
 
   // Queue `filter` ([M][C][3][3], fp32) for layout `kind`; Flush() issues the packs that are stale
   // (one multi-filter launch for the Winograd layouts) on `stream`; Packed() is valid after it.
@@ -42,7 +43,14 @@ class FilterPackCache {
     const bool dgrad = kind == WINO_DGRAD || kind == DIRECT_DGRAD || kind == WINO24_DGRAD || kind == SPLIT_DGRAD;
     const bool wino = kind == WINO_FWD || kind == WINO_DGRAD;
     const int po = dgrad ? C : M, pi = dgrad ? M : C;       // the pack's (outputs, inputs)
-    e.packed.Resize((TIndex)((kind == SPLIT_FWD || kind == SPLIT_DGRAD) ? ssad_conv_split_filter_floats(po, pi)
+    const bool grouped = kind == GROUPED_FWD || kind == GROUPED_DGRAD;
+    const long long gfloats = !grouped || C < 1 || M % C ? -1
+                              : kind == GROUPED_FWD ? ssad_grouped_conv3x3_filter_floats(M, M / C)
+                                                    : ssad_grouped_conv3x3_dgrad_filter_floats(M, M / C);
+    CAFFE_ENFORCE(!grouped || gfloats > 0, "grouped 3x3 engine: ", M, " channels with ", C,
+                  " per group (4, 8, 16, 32 or 64 per group)");
+    e.packed.Resize((TIndex)(grouped ? (size_t)gfloats
+                             : (kind == SPLIT_FWD || kind == SPLIT_DGRAD) ? ssad_conv_split_filter_floats(po, pi)
                              : (kind == WINO24_FWD || kind == WINO24_DGRAD) ? ssad_conv_wino24_filter_floats(po, pi)
                              : wino ? ssad_conv_wino_filter_floats(po, pi) : ssad_conv_packed_filter_floats(po, pi)));
     e.packed.mutable_data<float>();
@@ -68,6 +76,12 @@ class FilterPackCache {
           break;
         case DIRECT_DGRAD:
           CAFFE_ENFORCE_EQ(ssad_conv_pack_filter(e.src, e.M, e.C, nullptr, p, stream), 0);
+          break;
+        case GROUPED_FWD:
+          CAFFE_ENFORCE_EQ(ssad_grouped_conv3x3_pack_filter(e.src, e.M, e.M / e.C, p, stream), 0);
+          break;
+        case GROUPED_DGRAD:
+          CAFFE_ENFORCE_EQ(ssad_grouped_conv3x3_pack_filter_dgrad(e.src, e.M, e.M / e.C, p, stream), 0);
           break;
       }
       e.queued = false;

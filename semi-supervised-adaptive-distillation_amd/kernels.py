@@ -278,6 +278,13 @@ def lib():
     L.ssad_grouped_conv3x3_filter_floats.argtypes = [i32, i32]
     L.ssad_grouped_conv3x3_filter_floats.restype = C.c_longlong
     L.ssad_grouped_conv3x3_pack_filter.argtypes = [vp, i32, i32, vp, vp]
+    L.ssad_grouped_conv3x3_dgrad_filter_floats.argtypes = [i32, i32]
+    L.ssad_grouped_conv3x3_dgrad_filter_floats.restype = C.c_longlong
+    L.ssad_grouped_conv3x3_pack_filter_dgrad.argtypes = [vp, i32, i32, vp, vp]
+    L.ssad_grouped_conv3x3_dgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.ssad_grouped_conv3x3_wgrad_workspace_bytes.restype = sz
+    L.ssad_grouped_conv3x3_wgrad_workspace_bytes.argtypes = [i32] * 6
+    L.ssad_grouped_conv3x3_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]
     L.ssad_conv1x1_f16.argtypes = [C.POINTER(PwF16), vp]
     L.ssad_pw_f16_filter_halves.restype = sz
     L.ssad_pw_f16_filter_halves.argtypes = [i32, i32]
@@ -1362,6 +1369,63 @@ def grouped_conv3x3_forward(x, w, bias=None, group=64, stride=1, relu=False, out
     _check(lib().ssad_grouped_conv3x3_forward(_ptr(x), _ptr(packed), _ptr(bias), N, Cc, H, W, group, stride,
                                               int(relu), _ptr(y), _stream()), "grouped_conv3x3_forward")
     return y
+
+
+def _grouped_geometry(what, N, Cc, H, W, group, stride):
+    return "%s: N %d, %d channels in %d groups (4, 8, 16, 32 or 64 per group), %d x %d, stride %d (1 or 2)" % (
+        what, N, Cc, group, H, W, stride)
+
+
+def grouped_conv3x3_pack_filter_dgrad(w, group, out=None):
+    """[C][C/group][3][3] -> the grouped data gradient's operand order (per group transposed, taps flipped)."""
+    _f32c(w, "w")
+    Cc = w.shape[0]
+    n = lib().ssad_grouped_conv3x3_dgrad_filter_floats(Cc, group)
+    if n < 0 or w.shape[1] * group != Cc:
+        raise KernelError("grouped_conv3x3_dgrad: %d channels in %d groups (4, 8, 16, 32 or 64 per group)" % (Cc, group))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
+    _check(lib().ssad_grouped_conv3x3_pack_filter_dgrad(_ptr(w), Cc, group, _ptr(out), _stream()), "grouped dgrad pack")
+    return out
+
+
+def grouped_conv3x3_dgrad(dy, w, group, stride, in_hw, relu_x=None, out=None, packed=None):
+    """dX [N,C,H,W] of the grouped 3x3 / pad 1 convolution: dy [N,C,OH,OW], w [C, C/group, 3, 3] (or its dgrad pack),
+    in_hw = (H, W) of the input; relu_x: dX = 0 where relu_x <= 0 (ReluGradient of the layer below)."""
+    _f32c(dy, "dy")
+    N, Cc = dy.shape[0], dy.shape[1]
+    H, W = int(in_hw[0]), int(in_hw[1])
+    geo = _grouped_geometry("grouped_conv3x3_dgrad", N, Cc, H, W, group, stride)
+    if lib().ssad_grouped_conv3x3_dgrad_filter_floats(Cc, group) < 0 or stride not in (1, 2) or min(N, H, W) < 1:
+        raise KernelError(geo)
+    if tuple(dy.shape[2:]) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise KernelError(geo + ": dy is %s" % (tuple(dy.shape),))
+    if packed is None:
+        packed = grouped_conv3x3_pack_filter_dgrad(w, group)
+    if relu_x is not None:
+        _f32c(relu_x, "relu_x")
+    dx = out if out is not None else torch.empty((N, Cc, H, W), dtype=torch.float32, device="cuda")
+    _check(lib().ssad_grouped_conv3x3_dgrad(_ptr(dy), _ptr(packed), _ptr(relu_x), N, Cc, H, W, group, stride, _ptr(dx),
+                                            _stream()), geo)
+    return dx
+
+
+def grouped_conv3x3_wgrad(x, dy, group, stride, out=None, workspace=None):
+    """dW [C, C/group, 3, 3] of the grouped 3x3 / pad 1 convolution: x [N,C,H,W], dy [N,C,OH,OW].  workspace: a
+    device byte buffer of at least ssad_grouped_conv3x3_wgrad_workspace_bytes (the per-range partial sums)."""
+    _f32c(x, "x"); _f32c(dy, "dy")
+    N, Cc, H, W = x.shape
+    geo = _grouped_geometry("grouped_conv3x3_wgrad", N, Cc, H, W, group, stride)
+    nb = lib().ssad_grouped_conv3x3_wgrad_workspace_bytes(N, Cc, H, W, group, stride)
+    if nb == 0:
+        raise KernelError(geo)
+    if tuple(dy.shape) != (N, Cc, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise KernelError(geo + ": dy is %s" % (tuple(dy.shape),))
+    dw = out if out is not None else torch.empty((Cc, Cc // group, 3, 3), dtype=torch.float32, device="cuda")
+    ws = workspace if workspace is not None else _workspace(nb, "grouped_wgrad")
+    _check(lib().ssad_grouped_conv3x3_wgrad(_ptr(x), _ptr(dy), N, Cc, H, W, group, stride, _ptr(dw), _ptr(ws),
+                                            ws.numel() * ws.element_size(), _stream()), geo)
+    return dw
 
 
 def conv_implicit_gemm(x, w, bias=None, stride=1, pad=0, relu=False, out=None, split_k=False, wt=None):

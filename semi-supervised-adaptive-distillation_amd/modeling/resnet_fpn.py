@@ -64,6 +64,7 @@ class BodyConfig:
     k_min: int = 3                            # FPN.RPN_MIN_LEVEL
     k_max: int = 7                            # FPN.RPN_MAX_LEVEL
     use_cudnn_engine: bool = True             # keep the reference's engine="CUDNN" argument
+    grouped_engine: bool = False              # ResNeXt: hip_algo="grouped" on every bottleneck's grouped 3x3 Conv
 
     def widths(self, check=True):
         return channel_widths(self.channel_ratio, self.num_groups, self.width_per_group, self.fpn_dim, check)
@@ -111,10 +112,10 @@ class BodyModel:
         return self.net.AffineChannel([blob_in, s, b], blob_in if inplace else blob_out)
 
     def ConvAffine(self, blob_in, prefix, dim_in, dim_out, kernel, stride, pad, group=1, dilation=1,
-                   suffix="_bn", inplace=False):
+                   suffix="_bn", inplace=False, **kw):
         """detector.py:559-587."""
         c = self.Conv(blob_in, prefix, dim_in, dim_out, kernel, stride=stride, pad=pad, group=group,
-                      dilation=dilation, no_bias=1)
+                      dilation=dilation, no_bias=1, **kw)
         return self.AffineChannel(c, prefix + suffix, dim=dim_out, inplace=inplace)
 
     def Relu(self, blob_in, blob_out):
@@ -136,9 +137,12 @@ def bottleneck_transformation(model, blob_in, dim_in, dim_out, stride, prefix, d
     cur = model.ConvAffine(blob_in, prefix + "_branch2a", dim_in, dim_inner, kernel=1,
                            stride=str1x1, pad=0, inplace=True)
     cur = model.Relu(cur, cur)
+    # BodyConfig.grouped_engine: the grouped kernels instead of the default engine (an extension: the reference
+    # builder emits no such argument, and with the default neither does this one)
+    algo = dict(hip_algo="grouped") if model.cfg.grouped_engine and group > 1 else {}
     cur = model.ConvAffine(cur, prefix + "_branch2b", dim_inner, dim_inner, kernel=3,
                            stride=str3x3, pad=1 * dilation, dilation=dilation, group=group,
-                           inplace=True)
+                           inplace=True, **algo)
     cur = model.Relu(cur, cur)
     return model.ConvAffine(cur, prefix + "_branch2c", dim_inner, dim_out, kernel=1, stride=1,
                             pad=0, inplace=False)
