@@ -721,6 +721,21 @@ SSAD_API size_t ssad_grouped_conv3x3_wgrad_workspace_bytes(int N, int C, int H, 
 SSAD_API int ssad_grouped_conv3x3_wgrad(const float* x, const float* dy, int N, int C, int H, int W, int group,
                                         int stride, float* dw, void* workspace, size_t workspace_bytes,
                                         ssad_stream_t stream);
+/* Both packed copies of every trained grouped filter in ONE launch per <= 64 entries (grouped_pack.hip): the table
+ * travels in the kernel arguments (no device table, no host round trip), a workgroup finds its entry from a prefix table
+ * of block counts.  The five widths may be mixed in one table; pf / pd receive the same bits as
+ * ssad_grouped_conv3x3_pack_filter / _pack_filter_dgrad.  The whole table is checked before the first launch:
+ * SSAD_E_BADARG / -1 with nothing written for a width the kernels do not serve, C % group != 0, a missing w, both packs
+ * NULL, a NULL table or n_entries <= 0. */
+#define SSAD_MAX_GROUPED_PACK_ENTRIES 64   /* per launch; longer tables are chunked */
+typedef struct ssad_grouped_pack_entry {
+  const float* w;     /* [C][C/group][3][3] fp32 */
+  float* pf;          /* forward pack or NULL */
+  float* pd;          /* data-gradient pack or NULL (not both NULL) */
+  int C, group;
+} ssad_grouped_pack_entry;
+SSAD_API int ssad_grouped_conv3x3_pack_filters(const ssad_grouped_pack_entry* entries_host, int n_entries,
+                                               ssad_stream_t stream);
 /* MaxPool / MaxPoolGradient, NCHW (caffe2/operators/pool_op.cu): windows are clipped to
  * the image; every input equal to its window's maximum receives the gradient */
 SSAD_API int ssad_max_pool_forward(const float* x, int N, int C, int H, int W, int kh, int kw,

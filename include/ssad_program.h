@@ -193,7 +193,16 @@ enum ssad_opcode {
   SSAD_OP_GEMM_SPLIT_PACK = 82,
   /* ssad_softmax_focal_loss_fused(p0 = levels_host, i0 = n, p1 = fg_num, f0 = dloss, p2 = params_host, p3 = losses,
    * p4 = workspace, l0 = workspace_bytes) */
-  SSAD_OP_SOFTMAX_FOCAL_FUSED = 83
+  SSAD_OP_SOFTMAX_FOCAL_FUSED = 83,
+  /* a trained ResNeXt's grouped 3x3 (grouped_conv3x3_grad.hip, grouped_pack.hip) */
+  /* ssad_grouped_conv3x3_dgrad(p0 = dy, p1 = packed (data-gradient order), p2 = relu_x or NULL, i0..i3 = N, C, H, W of
+   * the INPUT, i4 = group, i5 = stride, p3 = dx) */
+  SSAD_OP_GROUPED_DGRAD = 84,
+  /* ssad_grouped_conv3x3_wgrad(p0 = x, p1 = dy, i0..i5 as above, p2 = dw, p3 = workspace, l0 = workspace bytes) */
+  SSAD_OP_GROUPED_WGRAD = 85,
+  /* ssad_grouped_conv3x3_pack_filters(p0 = const ssad_grouped_pack_entry* (host table, kept alive by the caller),
+   * i0 = entries) */
+  SSAD_OP_GROUPED_PACKS = 86
 };
 
 typedef struct ssad_op {

@@ -51,8 +51,9 @@ GEMM_SPLIT_MIN_PIXELS = 8192
 
 ARCHS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3), "x101-32x8d": (3, 4, 23, 3)}
 # ResNeXt (ResNet.py:247-258): name -> (groups, width per group); the stride sits on the 3x3
-# (RESNETS.STRIDE_1X1 = False).  Forward only: the frozen teachers of BASELINE config 5 (64x4d) and of the
-# reference's retinanet_X-101-32x8d-FPN configurations (groups 8, 16, 32 and 64 channels wide at res2..res5).
+# (RESNETS.STRIDE_1X1 = False).  By default forward only: the frozen teachers of BASELINE config 5 (64x4d) and of the
+# reference's retinanet_X-101-32x8d-FPN configurations (groups 8, 16, 32 and 64 channels wide at res2..res5); trained
+# with NativeResNetFPN(..., grouped_grad=True).
 GROUPED = {"x101-64x4d": (64, 4), "x101-32x8d": (32, 8)}
 
 
@@ -102,10 +103,16 @@ class _Layer(object):
 class NativeResNetFPN(object):
     def __init__(self, arch="r50", N=2, image_hw=(640, 896), device="cuda", train=True, src=None,
                  fpn_dim=256, lr=1e-5, momentum=0.9, weight_decay=1e-4, process_group=None, world_size=1,
-                 affine_scales=None, skip_flag=None, overlap_wgrad=None, channel_ratio=1.0):
+                 affine_scales=None, skip_flag=None, overlap_wgrad=None, channel_ratio=1.0, grouped_grad=False):
         """channel_ratio: RESNETS.CHANNEL_RATIO (ResNet.py:99-124, FPN.py:122,501), the width multiplier of a thin
         student; fpn_dim is FPN.DIM before the ratio, self.D = int(fpn_dim * channel_ratio) what the network builds
-        (and the subnets inherit).  The stem stays 64 wide."""
+        (and the subnets inherit).  The stem stays 64 wide.
+        grouped_grad: allow train=True on a grouped architecture (a ResNeXt student: the grouped 3x3 layers of
+        res3..res5 get the data and filter gradients of grouped_conv3x3_grad.hip).  Off by default: a ResNeXt is then
+        the frozen teacher only, as before.  No effect on the plain ResNets; fp32 backbone, channel_ratio 1 only."""
+        if grouped_grad and getattr(self, "F16", False):
+            raise K.KernelError("native backbone: grouped_grad with the fp16-storage backbone is not supported (the "
+                                "grouped 3x3 gradient kernels are fp32); use the fp32 backbone")
         if float(channel_ratio) != 1.0 and getattr(self, "F16", False):
             raise K.KernelError("native backbone: channel_ratio %r with the fp16-storage backbone is not supported "
                                 "(backbone_f16's kernels were written for the full widths); use the fp32 backbone"
@@ -114,7 +121,8 @@ class NativeResNetFPN(object):
         if getattr(self, "F16", False):
             check_f16_grouped(arch)
         self.channel_ratio = float(channel_ratio)
-        if arch in GROUPED and train:
+        self.grouped_grad = bool(grouped_grad)
+        if arch in GROUPED and train and not grouped_grad:
             raise K.KernelError("native backbone: %s is forward only (the frozen teacher); its grouped 3x3 has no "
                                 "gradient kernels" % arch)
         self.arch, self.N, self.hw, self.device, self.train = arch, N, tuple(image_hw), device, train
@@ -280,7 +288,7 @@ class NativeResNetFPN(object):
             if not l.train or l.affine:
                 l.b = self.frozen_flat[off:off + l.cout]
                 off += l.cout
-        n_train = sum(l.cout * l.cin * l.k * l.k + (0 if l.affine else l.cout) for l in order)
+        n_train = sum(l.cout * l.wcin * l.k * l.k + (0 if l.affine else l.cout) for l in order)
         self.params_flat = torch.empty(n_train, **f32)
         self.grads_flat = torch.zeros(n_train, **f32)
         self.moms_flat = torch.zeros(n_train, **f32)
@@ -290,16 +298,16 @@ class NativeResNetFPN(object):
             start = off
             for n in names:
                 l = L[n]
-                nw = l.cout * l.cin * l.k * l.k
-                l.w = self.params_flat[off:off + nw].view(l.cout, l.cin, l.k, l.k)
-                l.gw = self.grads_flat[off:off + nw].view(l.cout, l.cin, l.k, l.k)
+                nw = l.cout * l.wcin * l.k * l.k
+                l.w = self.params_flat[off:off + nw].view(l.cout, l.wcin, l.k, l.k)
+                l.gw = self.grads_flat[off:off + nw].view(l.cout, l.wcin, l.k, l.k)
                 sc = scales.get(n)
                 if sc is None and all_slots and l.affine:
                     sc = 1.0
                 if sc is not None and l.affine:
                     sc = torch.as_tensor(sc, dtype=torch.float32).reshape(-1).to(dev)
                     l.s2 = (sc * sc).expand(l.cout).contiguous() if sc.numel() == 1 else (sc * sc).contiguous()
-                self.segments.append((off, nw, 0, l.cin * l.k * l.k, l.s2))
+                self.segments.append((off, nw, 0, l.wcin * l.k * l.k, l.s2))
                 off += nw
                 if not l.affine:
                     l.b = self.params_flat[off:off + l.cout]
@@ -421,6 +429,36 @@ class NativeResNetFPN(object):
     def _wgrad3(self, P, x, dy, layer):
         emit_conv3x3_wgrad(P, (49, 70), [x], [dy], layer.gw, layer.gb, layer.cout, layer.cin,
                            backbone_wgrad_split(self.switches, layer.cout, layer.cin), self._amax, self._aux)
+
+    def _emit_grouped_packs(self, P, layers):
+        """One GROUPED_PACKS record: the forward and data-gradient packs of every trained grouped layer."""
+        tab = (K.GroupedPackEntry * len(layers))()
+        for k, l in enumerate(layers):
+            tab[k] = K.GroupedPackEntry(l.w.data_ptr(), l.pf.data_ptr(), l.pd.data_ptr(), l.cout, l.group)
+        self._grouped_pack_table = tab
+        P.add(PR.GROUPED_PACKS, 77, i=(len(layers),), p=(tab,),
+              work=4.0 * sum(l.w.numel() + l.pf.numel() + l.pd.numel() for l in layers),
+              keep=[t for l in layers for t in (l.w, l.pf, l.pd)])
+
+    def _wgrad_grouped(self, P, x, dy, layer):
+        """Filter gradient of a grouped 3x3 layer (x: what the layer read, at its own size; dy at the output's): on an
+        auxiliary stream like the others.  No bias gradient: the folded AffineChannel bias is frozen."""
+        N, Cc, H, W = x.shape
+        nb = K.lib().ssad_grouped_conv3x3_wgrad_workspace_bytes(N, Cc, H, W, layer.group, layer.stride)
+        if not nb:
+            raise K.KernelError("native backbone: %s: the grouped filter gradient refuses N %d, %d channels in %d groups, "
+                                "%d x %d, stride %d" % (layer.name, N, Cc, layer.group, H, W, layer.stride))
+        stream, ws = self._aux(P)
+        P.add(PR.GROUPED_WGRAD, 76, i=(N, Cc, H, W, layer.group, layer.stride), l=(nb,),
+              p=(x, dy, layer.gw, ws.need(nb)), keep=[x, dy],
+              work=2.0 * 9 * Cc * layer.wcin * N * dy.shape[2] * dy.shape[3], stream=stream)
+
+    def _dgrad_grouped(self, P, dy, dx, relu_x, layer):
+        """dx = ReluGradient(relu_x, grouped 3x3 data gradient of dy); H, W are dx's (the layer's input).  The kernel
+        folds no |max| word: dx's split-engine readers measure it (AmaxTable.measure in _gemm / _wgrad1)."""
+        N, Cc, H, W = dx.shape
+        P.add(PR.GROUPED_DGRAD, 75, i=(N, Cc, H, W, layer.group, layer.stride), p=(dy, layer.pd, relu_x, dx),
+              work=2.0 * 9 * Cc * layer.wcin * N * dy.shape[2] * dy.shape[3])
 
     def _wgrad1(self, P, x, dy, layer):
         N, Cc = x.shape[0], x.shape[1]
@@ -550,6 +588,7 @@ class NativeResNetFPN(object):
         self.amax = self._amax.tensor
         self._gemm_packs, self._gpack_train, self._gpack_frozen, self._a_train = {}, [], [], {}
         tr_frozen, tr_train = [], []          # (w, wt, M, K, ldm): every transposed filter of a program in one launch
+        gr_train = []                         # trained grouped 3x3 layers: their forward + data-gradient packs in one launch
         P.mark("pack")
         for l in L.values():
             tgt = P if l.train else prep
@@ -559,6 +598,10 @@ class NativeResNetFPN(object):
                 l.wt = self._t(l.cin, ldm)
                 trs.append((l.w, l.wt, l.cout, l.cin, ldm))
                 self._a_train[l.wt.data_ptr()] = self._a_train[l.w.data_ptr()] = l.train
+            elif l.k == 3 and l.group > 1 and l.train:           # ResNeXt student: both packs, every step, one launch
+                l.pf = self._t(lib.ssad_grouped_conv3x3_filter_floats(l.cout, l.group))
+                l.pd = self._t(lib.ssad_grouped_conv3x3_dgrad_filter_floats(l.cout, l.group))
+                gr_train.append(l)
             elif l.k == 3 and l.group > 1:                       # ResNeXt: MFMA operand order, packed once
                 l.pf = self._t(lib.ssad_grouped_conv3x3_filter_floats(l.cout, l.group))
                 tgt.add(PR.GROUPED_PACK, 54, i=(l.cout, l.group), p=(l.w, l.pf), work=4.0 * (l.w.numel() + l.pf.numel()))
@@ -586,6 +629,10 @@ class NativeResNetFPN(object):
                     tab[i] = K.TransposeEntry(w.data_ptr(), wt.data_ptr(), M, Kc, ldm, 0)
                 tgt.add(PR.TRANSPOSE_FILTERS, 54, i=(len(trs),), p=(tab,),
                         work=8.0 * sum(M * Kc for (_, _, M, Kc, _) in trs), keep=[t for e in trs for t in e[:2]])
+        if gr_train:
+            # as per-layer launches the two packs of an X-101's 30 trained grouped layers were a serial chain of 60
+            # kernels of a few microseconds at the head of the step (the transposes' story above)
+            self._emit_grouped_packs(P, gr_train)
         for tgt, train in ((prep, False), (P, True)):
             emit_packs(tgt, 54, packs[train], (Engine.F22, Engine.F24, Engine.SPLIT, Engine.DIRECT))
         # the pointwise filters' split copies (which layers need one is known once the passes are emitted: the table is
@@ -665,7 +712,7 @@ class NativeResNetFPN(object):
                 sc = self._t(N, cout, h, w)
                 self._gemm(P, lp.wt, lp.wt.shape[1], xs, sc, cin, cout, bias=lp.b)
             self._gemm(P, l3.wt, l3.wt.shape[1], y2, y, cmid, cout, bias=l3.b, res=sc, relu=True)
-            self.saved[pre] = dict(x=x, xs=xs, y1=y1, y2=y2, y=y)
+            self.saved[pre] = dict(x=x, xs=xs, y1=y1, y2=y2, y=y, c1_in=a)
             x = y
             stage_out[stage] = y
         c3, c4, c5 = stage_out[3], stage_out[4], stage_out[5]
@@ -801,15 +848,35 @@ class NativeResNetFPN(object):
             self._wgrad1(P, y2, dz, l3)
             dz2 = self._like(y2)
             self._gemm(P, l3.w.view(cout, cmid), cmid, dz, dz2, cout, cmid, mask=y2, fold=True)
-            self._wgrad3(P, y1, dz2, l2)                                   # + bias gradient of c2
             dz1 = self._like(y1)
-            self._conv3(P, [(dz2, dz1, y1, l2.pd, None)], cmid, cmid, K.CONV_MASK_AUX, l2.engine, fold=True)
-            self._wgrad1(P, xs, dz1, l1)
+            if l2.group > 1:
+                # ResNeXt: y1 (and so dz1) is at c1's input size, dz2 at the block's output size (stride on the 3x3)
+                self._wgrad_grouped(P, y1, dz2, l2)
+                self._dgrad_grouped(P, dz2, dz1, y1, l2)
+            else:
+                self._wgrad3(P, y1, dz2, l2)                               # + bias gradient of c2
+                self._conv3(P, [(dz2, dz1, y1, l2.pd, None)], cmid, cmid, K.CONV_MASK_AUX, l2.engine, fold=True)
+            sv["dz2"], sv["dz1"] = dz2, dz1
+            c1_in = sv["c1_in"]                                            # xs; the full map x in a ResNeXt
+            self._wgrad1(P, c1_in, dz1, l1)
             first_trainable = (stage == 3 and j == 0)
             if proj:
                 lp = L[pre + ".proj"]
                 self._wgrad1(P, xs, dz, lp)
-                if not first_trainable:
+                if not first_trainable and c1_in is not xs:
+                    # ResNeXt, stride 2: the two parts of the input gradient live at different sizes.  W1^T dz1 is
+                    # x-shaped: straight onto the previous stage's output gradient (which already holds the lateral's
+                    # part); Wp^T dz is xs-shaped: scattered onto it afterwards.  Always in this order: same bits.
+                    # (In place, unlike _aux's rule for gradients that meet: no auxiliary-stream launch reads tgt -- the
+                    # lateral's filter gradient reads the stage output and dt, not this buffer -- and its first reader,
+                    # the previous stage's ReluGradient, is emitted on the main stream behind both writes.)
+                    tgt = grads_into[stage - 1]
+                    self._gemm(P, l1.w.view(cmid, cin), cin, dz1, tgt, cmid, cin, acc=True)
+                    dxs = self._like(xs)
+                    self._gemm(P, lp.w.view(cout, cin), cin, dz, dxs, cout, cin)
+                    self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, cin, x.shape[2], x.shape[3], stride, 1), p=(dxs, tgt),
+                             nbytes=12.0 * tgt.numel())
+                elif not first_trainable:
                     dxs = self._like(xs)
                     self._gemm(P, l1.w.view(cmid, cin), cin, dz1, dxs, cmid, cin)
                     self._gemm(P, lp.w.view(cout, cin), cin, dz, dxs, cout, cin, acc=True)
@@ -910,7 +977,7 @@ class NativeDistillModel(object):
     def __init__(self, heads, student_arch="r50", teacher_arch="r101", N=16, image_hw=(640, 896), device="cuda",
                  process_group=None, world_size=1, lr=None, momentum=0.9, weight_decay=1e-4, two_streams=None,
                  overlap_wgrad=None, student_src=None, teacher_src=None, student_scales=None,
-                 student_channel_ratio=1.0):
+                 student_channel_ratio=1.0, student_grouped_grad=False):
         """lr: None = the subnets' learning rate (one schedule for the whole detector,
         optimizer.py:95-130).  two_streams / overlap_wgrad: None = environment
         (SSAD_NATIVE_TWO_STREAMS / SSAD_OVERLAP_WGRAD, default on).  *_src: initial weights
@@ -918,7 +985,8 @@ class NativeDistillModel(object):
         student_channel_ratio: RESNETS.CHANNEL_RATIO of the student (a thin student under a full-width teacher:
         the teacher is built from its own cfg, model_builder.py:384 switch_to_teacher(), ratio 1).  `heads` must have
         been built for the two widths: HeadConfig.fpn_dim = the student's FPN dimension, teacher_fpn_dim = the
-        teacher's (head_pipeline.DistillHeads)."""
+        teacher's (head_pipeline.DistillHeads).
+        student_grouped_grad: NativeResNetFPN's grouped_grad for the student (a ResNeXt student; fp32 backbones only)."""
         import os
         self.heads = heads
         self.student_channel_ratio = float(student_channel_ratio)
@@ -936,6 +1004,9 @@ class NativeDistillModel(object):
             raise K.KernelError("NativeDistillModel: student_channel_ratio %r with the fp16-storage backbones is not "
                                 "supported (backbone_f16's kernels were written for the full widths)"
                                 % (student_channel_ratio,))
+        if self.backbone_f16 and student_grouped_grad:
+            raise K.KernelError("NativeDistillModel: student_grouped_grad with the fp16-storage backbones is not "
+                                "supported (the grouped 3x3 gradient kernels are fp32); use the fp32 backbone")
         if self.backbone_f16:
             for arch in (student_arch, teacher_arch if self.has_teacher else None):
                 check_f16_grouped(arch)
@@ -957,7 +1028,8 @@ class NativeDistillModel(object):
                 world_size=world_size, heads_io=dict(fpn_out=heads.in_blk["teacher"])) if self.has_teacher else None
         else:
             self.student = NativeResNetFPN(student_arch, N, image_hw, device, train=True, src=student_src,
-                                           channel_ratio=student_channel_ratio, **kw)
+                                           channel_ratio=student_channel_ratio,
+                                           grouped_grad=student_grouped_grad, **kw)
             self.teacher = NativeResNetFPN(teacher_arch, N, image_hw, device, train=False, src=teacher_src,
                                            process_group=process_group,
                                            world_size=world_size) if self.has_teacher else None

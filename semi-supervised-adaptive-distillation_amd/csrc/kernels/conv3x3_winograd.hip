@@ -676,6 +676,16 @@ __global__ __launch_bounds__(kBlock, 1) void wino_conv_z_kernel(const WArgs args
       DBGW(s, 1);
     }
     DBG(1, s - 1, 4);
+    // A split unit drains the ring HERE.  The last chunk's steps 8..15 have just issued their (out-of-range) ring loads
+    // and nothing has waited for them; for hipcc the ring is dead from the loop's end to its re-definition below, and
+    // it hoists the start of the unit's epilogue into that gap.  In the build before this line the lane's slot offset
+    // (`my_off`, v_lshlrev_b32 v48) sat in v48 while v[48:51] was one of the eight ring slots: beside another stream's
+    // traffic the ring load landed after the shift and zeroed the offset, and the unit's partial sums went to another
+    // place in the slot (tools/kernel_stress.py, the split-tail cases: 12-33 of 60 iterations differed, never on a
+    // quiet chip; with this line, same call, none).  The "+v" operands of the wait keep the eight slots live up to
+    // it, so nothing else can be allocated to them while a load is in flight.  (tools/isa_lint.py reports compiler READS of an
+    // in-flight destination; a compiler write releases the register there, so this was not reported.)
+    if (SPLIT) ring_landed(ar);
     // The next tile's first operands and bias fly during the epilogue -- every wave, active or not, and also after
     // the last tile (Tn = T then: a harmless re-read), so that the ring has ONE definition at this point (see a_load)
 #pragma unroll

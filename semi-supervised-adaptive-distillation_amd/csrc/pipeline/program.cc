@@ -248,6 +248,14 @@ int run_op(const ssad_op& o, ssad_stream_t s) {
     case SSAD_OP_CONV_KXK_DGRAD:
       return ssad_conv_kxk_dgrad((const float*)p[0], (const float*)p[1], i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7],
                                  (float*)p[2], (const float*)p[4], (int)o.l[1], (void*)p[3], (size_t)o.l[0], s);
+    case SSAD_OP_GROUPED_DGRAD:
+      return ssad_grouped_conv3x3_dgrad((const float*)p[0], (const float*)p[1], (const float*)p[2], i[0], i[1], i[2],
+                                        i[3], i[4], i[5], (float*)p[3], s);
+    case SSAD_OP_GROUPED_WGRAD:
+      return ssad_grouped_conv3x3_wgrad((const float*)p[0], (const float*)p[1], i[0], i[1], i[2], i[3], i[4], i[5],
+                                        (float*)p[2], (void*)p[3], (size_t)o.l[0], s);
+    case SSAD_OP_GROUPED_PACKS:
+      return ssad_grouped_conv3x3_pack_filters((const ssad_grouped_pack_entry*)p[0], i[0], s);
     default:
       return SSAD_E_BADARG;
   }

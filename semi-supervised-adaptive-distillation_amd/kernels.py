@@ -70,6 +70,11 @@ class F16PackEntry(C.Structure):
                 ("taps", C.c_int), ("reserved", C.c_int)]
 
 
+class GroupedPackEntry(C.Structure):
+    """ssad_grouped_pack_entry (include/ssad_kernels.h): one grouped 3x3 filter and its forward / data-gradient packs."""
+    _fields_ = [("w", C.c_void_p), ("pf", C.c_void_p), ("pd", C.c_void_p), ("C", C.c_int), ("group", C.c_int)]
+
+
 class SgdSegment(C.Structure):
     _fields_ = [("offset", C.c_int64), ("n", C.c_int64), ("is_bias", C.c_int), ("row_len", C.c_int),
                 ("row_scale", C.c_void_p)]
@@ -285,6 +290,7 @@ def lib():
     L.ssad_grouped_conv3x3_wgrad_workspace_bytes.restype = sz
     L.ssad_grouped_conv3x3_wgrad_workspace_bytes.argtypes = [i32] * 6
     L.ssad_grouped_conv3x3_wgrad.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]
+    L.ssad_grouped_conv3x3_pack_filters.argtypes = [C.POINTER(GroupedPackEntry), i32, vp]
     L.ssad_conv1x1_f16.argtypes = [C.POINTER(PwF16), vp]
     L.ssad_pw_f16_filter_halves.restype = sz
     L.ssad_pw_f16_filter_halves.argtypes = [i32, i32]
@@ -1426,6 +1432,33 @@ def grouped_conv3x3_wgrad(x, dy, group, stride, out=None, workspace=None):
     _check(lib().ssad_grouped_conv3x3_wgrad(_ptr(x), _ptr(dy), N, Cc, H, W, group, stride, _ptr(dw), _ptr(ws),
                                             ws.numel() * ws.element_size(), _stream()), geo)
     return dw
+
+
+def grouped_conv3x3_pack_filters(entries):
+    """entries: [(w [C, C/group, 3, 3], group, pf or None, pd or None)]: the forward and / or data-gradient pack of
+    every filter in one launch per 64 entries (ssad_grouped_conv3x3_pack_filters); widths may be mixed.  The whole table
+    is checked before anything is written."""
+    if not entries:
+        raise KernelError("grouped_conv3x3_pack_filters: an empty table")
+    tab = (GroupedPackEntry * len(entries))()
+    for k, (w, group, pf, pd) in enumerate(entries):
+        _f32c(w, "w")
+        Cc = w.shape[0]
+        n = lib().ssad_grouped_conv3x3_filter_floats(Cc, group)
+        if w.dim() != 4 or n < 0 or w.shape[1] * group != Cc or tuple(w.shape[2:]) != (3, 3):
+            raise KernelError("grouped_conv3x3_pack_filters: entry %d: a %s filter in %d groups (4, 8, 16, 32 or 64 "
+                              "channels per group)" % (k, tuple(w.shape), group))
+        if pf is None and pd is None:
+            raise KernelError("grouped_conv3x3_pack_filters: entry %d has neither pack" % k)
+        for name, t in (("pf", pf), ("pd", pd)):
+            if t is not None:
+                _f32c(t, name)
+                if t.numel() < n:
+                    raise KernelError("grouped_conv3x3_pack_filters: entry %d: %s holds %d floats, the pack has %d"
+                                      % (k, name, t.numel(), n))
+        tab[k] = GroupedPackEntry(w.data_ptr(), pf.data_ptr() if pf is not None else None,
+                                  pd.data_ptr() if pd is not None else None, Cc, group)
+    _check(lib().ssad_grouped_conv3x3_pack_filters(tab, len(entries), _stream()), "grouped_conv3x3_pack_filters")
 
 
 def conv_implicit_gemm(x, w, bias=None, stride=1, pad=0, relu=False, out=None, split_k=False, wt=None):

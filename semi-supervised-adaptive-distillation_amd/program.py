@@ -30,6 +30,7 @@ CONV_IMPLICIT_WS, CONV_KXK_WGRAD, CONV_KXK_DGRAD, TRANSPOSE_FILTERS, F16_PACK_FI
 GEMM_CONV_SPLIT = 79
 SPLIT_ABSMAX_LEVELS, SPLIT_ABSMAX, GEMM_SPLIT_PACK = 80, 81, 82
 SOFTMAX_FOCAL_FUSED = 83
+GROUPED_DGRAD, GROUPED_WGRAD, GROUPED_PACKS = 84, 85, 86
 
 # timing classes: one per kernel family.  bound "mfma": work = direct-form FLOPs
 # (2*9*Cout*Cin per output pixel; the Winograd engine executes 1/2.25 of them);
@@ -111,6 +112,13 @@ KLASS = {
     53: dict(name="stem 7x7/2 conv (implicit GEMM: gemm_conv_nn_kernel<64, true>)", bound="mfma", wino=False),
     54: dict(name="backbone filter packs (transpose / Winograd)", bound="hbm"),
     56: dict(name="grouped 3x3 conv, ResNeXt (grouped_conv3x3_kernel)", bound="mfma", wino=False),
+    # a trained ResNeXt (NativeResNetFPN(grouped_grad=True)): work = direct-form FLOPs of the grouped product
+    75: dict(name="grouped 3x3 data gradient, ResNeXt student (grouped_dgrad_kernel, fused ReluGradient mask)",
+             bound="mfma", wino=False),
+    76: dict(name="grouped 3x3 filter gradient, ResNeXt student (grouped_wgrad_kernel + reduce in range order)",
+             bound="mfma", wino=False),
+    77: dict(name="grouped 3x3 filter packs, forward + data-gradient order, every trained layer in one launch "
+                  "(grouped_pack_multi_kernel)", bound="hbm"),
     55: dict(name="backbone momentum SGD (sgd_flat_kernel)", bound="hbm"),
     66: dict(name="backbone conv3x3 fwd/dgrad, >= 256 wide, split-operand engine (conv3x3_split_kernel + passes; SSAD_SPLIT_CONV & 16)",
              bound="mfma16", wino=True, exec_div=1.0 / 3.0),
