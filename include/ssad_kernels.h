@@ -1146,6 +1146,19 @@ SSAD_API int ssad_grouped_conv3x3_f16_pack_filter(const float* w, int C, int gro
                                                   ssad_stream_t stream);
 SSAD_API int ssad_grouped_conv3x3_f16(const void* x_blocked, const void* packed, const float* bias, int N, int C,
                                       int H, int W, int group, int relu, void* y_blocked, ssad_stream_t stream);
+/* The same layer for groups of 64 channels (res5 of ResNeXt-101-32x8d), as entry points of their own: the three
+ * above keep refusing C / group == 64.  C % 64 == 0 and C / group == 64, anything else is SSAD_E_BADARG (the size
+ * query returns 0); N == 0 returns 0.  A group is one workgroup's 64-channel slab: wave w holds output channels
+ * 16 w .. 16 w + 15 of the group and issues two v_mfma_f32_16x16x32_f16 per tap (input channels 0..31 and 32..63).
+ * The pack is a permutation of the rounded filter, C * 64 * 9 halves: [C/16][tap][half][lane][8], lane (i16, g4)
+ * holding w[16 sg + i16][32 half + 8 g4 .. + 7][tap].  No operand spans two groups, so a non-finite input stays in
+ * its group without a second pass.  fp32 accumulation, bias + ReLU in the epilogue, stride 1 (a stride-2 layer runs
+ * at stride 1 and keeps the even positions: ssad_f16_elementwise). */
+SSAD_API size_t ssad_grouped_conv3x3_f16_cg64_filter_halves(int C, int group);
+SSAD_API int ssad_grouped_conv3x3_f16_cg64_pack_filter(const float* w, int C, int group, void* packed,
+                                                       ssad_stream_t stream);
+SSAD_API int ssad_grouped_conv3x3_f16_cg64(const void* x_blocked, const void* packed, const float* bias, int N, int C,
+                                           int H, int W, int group, int relu, void* y_blocked, ssad_stream_t stream);
 
 /* Plain fp32 GEMM on the matrix cores (exact fp32 v_mfma_f32_32x32x2_f32): row-major
  * C[M x N] = alpha op(A) op(B) + beta C for `batch` problems `stride_*` elements apart -- math::Gemm /

@@ -202,7 +202,12 @@ enum ssad_opcode {
   SSAD_OP_GROUPED_WGRAD = 85,
   /* ssad_grouped_conv3x3_pack_filters(p0 = const ssad_grouped_pack_entry* (host table, kept alive by the caller),
    * i0 = entries) */
-  SSAD_OP_GROUPED_PACKS = 86
+  SSAD_OP_GROUPED_PACKS = 86,
+  /* the fp16 grouped 3x3 for 64-wide groups (ssad_grouped_conv3x3_f16_cg64*): operands as records 72 and 73 */
+  /* i0..i5 = N, C, H, W, group, relu; p0 = x, p1 = packed, p2 = bias, p3 = y */
+  SSAD_OP_GROUPED_F16_CG64 = 87,
+  /* i0 = C, i1 = group; p0 = w, p1 = packed */
+  SSAD_OP_GROUPED_F16_CG64_PACK = 88
 };
 
 typedef struct ssad_op {

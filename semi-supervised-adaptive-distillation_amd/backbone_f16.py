@@ -15,7 +15,8 @@ Kernels:
     shortcut Sum, ReLU, FPN's top-down upsample + Sum (forward) and the ReluGradient mask / gradient
     Sum (data gradient) in the epilogue; filter gradient = conv3x3_wgrad_f16_kernel<true>;
   * 3x3 / stride 1: conv3x3_f16.hip (forward, masked data gradient, filter + bias gradient);
-  * ResNeXt's grouped 3x3 (the X-101-64x4d teacher): grouped_f16.hip, forward;
+  * ResNeXt's grouped 3x3 (the X-101-64x4d teacher): grouped_f16.hip, forward; with wide_groups=True also the
+    X-101-32x8d teacher, whose three 64-wide res5 layers take that file's 64-wide entry points;
   * stride-2 3x3 layers (P6, P7, ResNeXt's first blocks): the stride-1 layer + the even positions;
   * the 7x7 / 2 stem: the fp32 implicit GEMM on the fp32 image (Cin = 3), then bias + ReLU +
     3x3 / 2 max pool written blocked fp16 (ssad_stem_pool_f16);
@@ -36,11 +37,16 @@ class NativeResNetFPNF16(NativeResNetFPN):
     """heads_io (optional): dict(fpn_out=[5 blocked fp16 tensors the FPN levels are written into],
     d_fpn_in=([5], [5]) the two blocked fp16 gradient sets to be summed (cls / bbox subnet),
     inv_scale=1-element float32 device tensor holding 1 / loss scale).  Without it the network owns
-    its FPN outputs (self.fpn, blocked fp16) and gradient inputs (self.d_fpn)."""
+    its FPN outputs (self.fpn, blocked fp16) and gradient inputs (self.d_fpn).
+    wide_groups: accept a ResNeXt whose res5 groups are 64 wide (x101-32x8d): those layers get the GROUPED_F16_CG64
+    records, every narrower layer the records it always had.  Off by default (the architecture is then refused, as
+    before); no effect on any other architecture.  Forward only, like every grouped fp16 network."""
 
     F16 = True
 
-    def __init__(self, arch="r50", N=2, image_hw=(640, 896), device="cuda", train=True, heads_io=None, **kw):
+    def __init__(self, arch="r50", N=2, image_hw=(640, 896), device="cuda", train=True, heads_io=None,
+                 wide_groups=False, **kw):
+        self.wide_groups = bool(wide_groups)
         self._io = heads_io or {}
         self._act = []
         super().__init__(arch, N, image_hw, device, train=train, **kw)
@@ -133,10 +139,12 @@ class NativeResNetFPNF16(NativeResNetFPN):
                 l.pd = torch.empty(n, **h16) if l.train else None
                 packs[bool(l.train)].append((l.w, l.pf, l.pd, l.cout, l.cin, 1 if l.k == 1 else 9))
             elif l.k == 3:
-                n = lib.ssad_grouped_conv3x3_f16_filter_halves(l.cout, l.group)
+                cg64 = l.wcin == 64                                  # (only behind wide_groups: check_f16_grouped)
+                n = (lib.ssad_grouped_conv3x3_f16_cg64_filter_halves if cg64
+                     else lib.ssad_grouped_conv3x3_f16_filter_halves)(l.cout, l.group)
                 l.pf = torch.empty(n, **h16)
-                tgt.add(PR.GROUPED_F16_PACK, KL_PACK, i=(l.cout, l.group), p=(l.w, l.pf),
-                        work=4.0 * l.w.numel() + 2.0 * n)
+                tgt.add(PR.GROUPED_F16_CG64_PACK if cg64 else PR.GROUPED_F16_PACK, KL_PACK, i=(l.cout, l.group),
+                        p=(l.w, l.pf), work=4.0 * l.w.numel() + 2.0 * n)
             else:                                                    # stem: fp32 [147][64] (Cin = 3)
                 l.wt = self._t(l.cin * l.k * l.k, l.cout)
                 tgt.add(PR.TRANSPOSE_FILTER, 54, i=(l.cout, l.cin * l.k * l.k, l.cout), p=(l.w, l.wt),
@@ -202,7 +210,8 @@ class NativeResNetFPNF16(NativeResNetFPN):
             self._pw(P, a, l1.pf, y1, cin, cmid, bias=l1.b, relu=True)
             if l2.group > 1:
                 y2f = y2 if l2.stride == 1 else self._b(N, cmid, y1.shape[2], y1.shape[3])
-                P.add(PR.GROUPED_F16, KL_GR, i=(N, cmid, y1.shape[2], y1.shape[3], l2.group, 1),
+                P.add(PR.GROUPED_F16_CG64 if l2.wcin == 64 else PR.GROUPED_F16, KL_GR,
+                      i=(N, cmid, y1.shape[2], y1.shape[3], l2.group, 1),
                       p=(y1, l2.pf, l2.b, y2f), work=2.0 * 9 * cmid * l2.wcin * N * y1.shape[2] * y1.shape[3],
                       keep=[y1, y2f])
                 if l2.stride != 1:                             # ReLU commutes with taking the even positions

@@ -57,10 +57,12 @@ ARCHS = {"r50": (3, 4, 6, 3), "r101": (3, 4, 23, 3), "x101-64x4d": (3, 4, 23, 3)
 GROUPED = {"x101-64x4d": (64, 4), "x101-32x8d": (32, 8)}
 
 
-def check_f16_grouped(arch):
+def check_f16_grouped(arch, wide_groups=False):
     """The fp16-storage backbone's grouped 3x3 (grouped_f16.hip) serves groups of up to 32 channels; a ResNeXt whose
-    res5 groups (8 x width per group) are wider is an fp32 network only.  Raises KernelError; touches no device."""
-    if arch in GROUPED and 8 * GROUPED[arch][1] > 32:
+    res5 groups (8 x width per group) are wider is an fp32 network only -- unless wide_groups asks for the 64-wide
+    entry points (ssad_grouped_conv3x3_f16_cg64), which take res5 groups of exactly 64.  Raises KernelError; touches no
+    device."""
+    if arch in GROUPED and 8 * GROUPED[arch][1] > (64 if wide_groups else 32):
         raise K.KernelError("native backbone: %s has no fp16-storage backbone: the fp16 grouped kernel stops at "
                             "32-wide groups and its res5 groups are %d wide; use the fp32 backbone"
                             % (arch, 8 * GROUPED[arch][1]))
@@ -119,7 +121,7 @@ class NativeResNetFPN(object):
                                 % (channel_ratio,))
         self.widths = student_widths(arch, channel_ratio, fpn_dim)       # (before anything touches the library)
         if getattr(self, "F16", False):
-            check_f16_grouped(arch)
+            check_f16_grouped(arch, getattr(self, "wide_groups", False))
         self.channel_ratio = float(channel_ratio)
         self.grouped_grad = bool(grouped_grad)
         if arch in GROUPED and train and not grouped_grad:
@@ -977,7 +979,7 @@ class NativeDistillModel(object):
     def __init__(self, heads, student_arch="r50", teacher_arch="r101", N=16, image_hw=(640, 896), device="cuda",
                  process_group=None, world_size=1, lr=None, momentum=0.9, weight_decay=1e-4, two_streams=None,
                  overlap_wgrad=None, student_src=None, teacher_src=None, student_scales=None,
-                 student_channel_ratio=1.0, student_grouped_grad=False):
+                 student_channel_ratio=1.0, student_grouped_grad=False, teacher_wide_groups=False):
         """lr: None = the subnets' learning rate (one schedule for the whole detector,
         optimizer.py:95-130).  two_streams / overlap_wgrad: None = environment
         (SSAD_NATIVE_TWO_STREAMS / SSAD_OVERLAP_WGRAD, default on).  *_src: initial weights
@@ -986,7 +988,9 @@ class NativeDistillModel(object):
         the teacher is built from its own cfg, model_builder.py:384 switch_to_teacher(), ratio 1).  `heads` must have
         been built for the two widths: HeadConfig.fpn_dim = the student's FPN dimension, teacher_fpn_dim = the
         teacher's (head_pipeline.DistillHeads).
-        student_grouped_grad: NativeResNetFPN's grouped_grad for the student (a ResNeXt student; fp32 backbones only)."""
+        student_grouped_grad: NativeResNetFPN's grouped_grad for the student (a ResNeXt student; fp32 backbones only).
+        teacher_wide_groups: NativeResNetFPNF16's wide_groups for the fp16 teacher (x101-32x8d, whose res5 groups are 64
+        wide); the fp32 backbones run that teacher already and ignore it."""
         import os
         self.heads = heads
         self.student_channel_ratio = float(student_channel_ratio)
@@ -1008,8 +1012,9 @@ class NativeDistillModel(object):
             raise K.KernelError("NativeDistillModel: student_grouped_grad with the fp16-storage backbones is not "
                                 "supported (the grouped 3x3 gradient kernels are fp32); use the fp32 backbone")
         if self.backbone_f16:
-            for arch in (student_arch, teacher_arch if self.has_teacher else None):
-                check_f16_grouped(arch)
+            check_f16_grouped(student_arch)
+            if self.has_teacher:
+                check_f16_grouped(teacher_arch, teacher_wide_groups)
         want_s = student_widths(student_arch, student_channel_ratio).fpn_dim      # (raises before any allocation)
         if getattr(heads, "D", want_s) != want_s:
             raise K.KernelError("NativeDistillModel: the subnets were built for FPN dimension %d, a %s student of "
@@ -1025,7 +1030,8 @@ class NativeDistillModel(object):
                               d_fpn_in=(heads.dbuf["cls"][0], heads.dbuf["bbox"][0])), **kw)
             self.teacher = NativeResNetFPNF16(
                 teacher_arch, N, image_hw, device, train=False, src=teacher_src, process_group=process_group,
-                world_size=world_size, heads_io=dict(fpn_out=heads.in_blk["teacher"])) if self.has_teacher else None
+                world_size=world_size, heads_io=dict(fpn_out=heads.in_blk["teacher"]),
+                wide_groups=teacher_wide_groups) if self.has_teacher else None
         else:
             self.student = NativeResNetFPN(student_arch, N, image_hw, device, train=True, src=student_src,
                                            channel_ratio=student_channel_ratio,

@@ -24,6 +24,14 @@
 //     zeroed LDS region, and a lane keeps the accumulator of the group its four output rows belong to.  Finite data
 //     never takes that path and runs the instructions it ran before;
 //   * epilogue: bias (the folded AffineChannel) + ReLU, 8-byte stores.
+//
+// Groups of 64 (res5 of X-101-32x8d) are a third mode of the same kernel behind entry points of their own
+// (ssad_grouped_conv3x3_f16_cg64*; the narrow launchers keep refusing the width): the workgroup's 64-channel slab IS
+// the group, wave w holds its output channels 16 w .. 16 w + 15, K = 64 per tap = two instructions (18 per row
+// segment), each k-group still one 16-byte LDS read.  NG = 1 and no operand spans two groups: no recompute pass.
+// The 18 operands stay in registers: 124 VGPRs, four waves per SIMD (four of the six workgroups a CU's LDS holds),
+// two row segments interleaved -- measured against one chain at five waves (1.2-1.3 x slower) and against the fully
+// unrolled form at three waves (equal within the spread): profiles/x101_32x8d_f16.md.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,10 +75,15 @@ __device__ __forceinline__ half8 as_half8(const uint4& v) { return __builtin_bit
 // NG: groups inside a 16-channel super-group (1 for groups of 16 and 32, 2 for groups of 8, 4 for groups of 4)
 // (NG > 1 keeps a tile's eight accumulators; six waves per SIMD -- the six workgroups a CU's LDS holds -- bound the
 // registers the scheduler may spend on hoisting the LDS reads of all eight row segments)
-template <bool WIDE, int NG>
-__global__ __launch_bounds__(kThreads, NG > 1 ? 6 : 1) void grouped_f16_kernel(const GroupedF16 p) {
-  constexpr int MF = WIDE ? 9 : 5;
+// CG64 = true (with WIDE, NG = 1): groups of 64 = the workgroup's whole slab.  MF = 18: instruction 2 tap + h covers
+// input channels 32 h .. 32 h + 31 of the group at that tap, so its k-group g4 reads block 4 h + g4 and every wave
+// reads all eight blocks.  The 18 operands stay in registers (72 VGPRs): four waves per SIMD, i.e. four of the six
+// workgroups a CU's LDS would hold; two row segments are issued interleaved so that no MFMA waits for the one before.
+template <bool WIDE, int NG, bool CG64 = false>
+__global__ __launch_bounds__(kThreads, CG64 ? 4 : NG > 1 ? 6 : 1) void grouped_f16_kernel(const GroupedF16 p) {
+  constexpr int MF = CG64 ? 18 : WIDE ? 9 : 5;
   static_assert(!WIDE || NG == 1, "a group of 32 is two operands wide");
+  static_assert(!CG64 || WIDE, "a group of 64 is four operands wide");
   __shared__ uint4 lds[NG > 1 ? ZB + TR * HC : PIECES * 64];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -109,6 +122,7 @@ __global__ __launch_bounds__(kThreads, NG > 1 ? 6 : 1) void grouped_f16_kernel(c
   }
   // B operand slot of lane (pixel i16, k-group g4) for instruction mf, row segment r:
   //   narrow: tap = 2 mf + (g4 >> 1), block = 2 wave + (g4 & 1);  wide: tap = mf, block = 4 (wave / 2) + g4
+  //   (groups of 64 address LDS below, from one register)
   int boff[MF];
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf) {
@@ -154,6 +168,26 @@ __global__ __launch_bounds__(kThreads, NG > 1 ? 6 : 1) void grouped_f16_kernel(c
                             : kOob;
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2v, o), yrs, vo, 0, 0);
   };
+  if (CG64) {
+    // instruction mf = 2 tap + h, k-group g4: block 4 h + g4, pixel i16 shifted by the tap.  One address register:
+    // the slot is (g4 HR HC + i16) + a constant of (mf, r), the instruction's immediate offset
+    const uint4* lb = lds + g4 * (HR * HC) + i16;
+#pragma unroll 1
+    for (int r = 0; r < TR; r += 2) {                        // two independent chains of 18
+      float4v acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf) {
+        const int c = (4 * (mf & 1) * HR + (mf >> 1) / 3 + r) * HC + (mf >> 1) % 3;
+        const half8 b0 = as_half8(lb[c]);
+        const half8 b1 = as_half8(lb[c + HC]);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mf], b0, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[mf], b1, acc1, 0, 0, 0);
+      }
+      store(r, acc0);
+      store(r + 1, acc1);
+    }
+    return;
+  }
   if (NG == 1) {
 #pragma unroll
     for (int r = 0; r < TR; ++r) store(r, fast(r));
@@ -234,6 +268,22 @@ __global__ __launch_bounds__(kThreads) void grouped_f16_pack_kernel(const float*
   out[idx] = __builtin_bit_cast(uint4, o);
 }
 
+// groups of 64: w [C][64][3][3] fp32 -> [C/16][18][64][8] fp16, instruction 2 tap + h: a permutation, no zero slot
+__global__ __launch_bounds__(kThreads) void grouped_f16_cg64_pack_kernel(const float* __restrict__ w, int C,
+                                                                         uint4* __restrict__ out) {
+  const int total = (C / 16) * 18 * 64;
+  const int idx = blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= total) return;
+  const int lane = idx & 63, mf = (idx >> 6) % 18, sg = (idx >> 6) / 18;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int m = sg * 16 + i16;
+  const int ci = 32 * (mf & 1) + 8 * g4;                   // first of the lane's 8 channels inside the group
+  half8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (_Float16)w[((long long)m * 64 + ci + e) * 9 + (mf >> 1)];
+  out[idx] = __builtin_bit_cast(uint4, o);
+}
+
 }  // namespace
 
 extern "C" {
@@ -277,6 +327,43 @@ int ssad_grouped_conv3x3_f16(const void* x_blocked, const void* packed, const fl
   else if (cg == 16) hipLaunchKernelGGL((grouped_f16_kernel<false, 1>), grid, block, 0, (hipStream_t)stream, p);
   else if (cg == 8) hipLaunchKernelGGL((grouped_f16_kernel<false, 2>), grid, block, 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL((grouped_f16_kernel<false, 4>), grid, block, 0, (hipStream_t)stream, p);
+  return (int)hipGetLastError();
+}
+
+// ---- groups of 64 (ResNeXt-101-32x8d's res5): entry points of their own, the ones above keep refusing the width
+
+size_t ssad_grouped_conv3x3_f16_cg64_filter_halves(int C, int group) {
+  if (C < 64 || group < 1 || (C & 63) || C % group || C / group != 64) return 0;
+  return (size_t)C * 64 * 9;
+}
+
+int ssad_grouped_conv3x3_f16_cg64_pack_filter(const float* w, int C, int group, void* packed, ssad_stream_t stream) {
+  if (!w || !packed || C < 64 || (C & 63) || group < 1 || C % group || C / group != 64) return SSAD_E_BADARG;
+  const int total = (C / 16) * 18 * 64;
+  hipLaunchKernelGGL(grouped_f16_cg64_pack_kernel, dim3((total + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                     (hipStream_t)stream, w, C, static_cast<uint4*>(packed));
+  return (int)hipGetLastError();
+}
+
+int ssad_grouped_conv3x3_f16_cg64(const void* x_blocked, const void* packed, const float* bias, int N, int C, int H,
+                                  int W, int group, int relu, void* y_blocked, ssad_stream_t stream) {
+  if (!x_blocked || !packed || !y_blocked || N < 0 || C < 64 || (C & 63) || H < 1 || W < 1 || group < 1 ||
+      C % group || C / group != 64)
+    return SSAD_E_BADARG;
+  if (N == 0) return 0;
+  if ((long long)N * (C >> 3) * H * W * 16 >= (1LL << 31)) return SSAD_E_BADARG;
+  GroupedF16 p;
+  p.x = static_cast<const uint4*>(x_blocked);
+  p.w = static_cast<const uint4*>(packed);
+  p.bias = bias;
+  p.y = static_cast<uint4*>(y_blocked);
+  p.N = N; p.C = C; p.H = H; p.W = W;
+  p.tiles_x = (W + TC - 1) / TC; p.tiles_y = (H + TR - 1) / TR; p.slabs = C / 64;
+  p.relu = relu;
+  const long long wgs = (long long)N * p.tiles_x * p.tiles_y * p.slabs;
+  if (wgs >= (1LL << 31)) return SSAD_E_BADARG;
+  hipLaunchKernelGGL((grouped_f16_kernel<true, 1, true>), dim3((unsigned)wgs), dim3(kThreads), 0, (hipStream_t)stream,
+                     p);
   return (int)hipGetLastError();
 }
 

@@ -235,6 +235,11 @@ int run_op(const ssad_op& o, ssad_stream_t s) {
                                       (void*)p[3], s);
     case SSAD_OP_GROUPED_F16_PACK:
       return ssad_grouped_conv3x3_f16_pack_filter((const float*)p[0], i[0], i[1], (void*)p[1], s);
+    case SSAD_OP_GROUPED_F16_CG64:
+      return ssad_grouped_conv3x3_f16_cg64(p[0], p[1], (const float*)p[2], i[0], i[1], i[2], i[3], i[4], i[5],
+                                           (void*)p[3], s);
+    case SSAD_OP_GROUPED_F16_CG64_PACK:
+      return ssad_grouped_conv3x3_f16_cg64_pack_filter((const float*)p[0], i[0], i[1], (void*)p[1], s);
     case SSAD_OP_TRANSPOSE_FILTERS:
       return ssad_transpose_filters((const ssad_transpose_entry*)p[0], i[0], s);
     case SSAD_OP_F16_PACK_FILTERS:

@@ -305,6 +305,10 @@ def lib():
     L.ssad_grouped_conv3x3_f16_filter_halves.argtypes = [i32, i32]
     L.ssad_grouped_conv3x3_f16_pack_filter.argtypes = [vp, i32, i32, vp, vp]
     L.ssad_grouped_conv3x3_f16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.ssad_grouped_conv3x3_f16_cg64_filter_halves.restype = sz
+    L.ssad_grouped_conv3x3_f16_cg64_filter_halves.argtypes = [i32, i32]
+    L.ssad_grouped_conv3x3_f16_cg64_pack_filter.argtypes = [vp, i32, i32, vp, vp]
+    L.ssad_grouped_conv3x3_f16_cg64.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     L.ssad_image_blobs_workspace_bytes.restype = sz
     L.ssad_image_blobs_workspace_bytes.argtypes = [i32, i32, i32]
     L.ssad_image_blobs.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(ImageNorm), i32,
@@ -1375,6 +1379,59 @@ def grouped_conv3x3_forward(x, w, bias=None, group=64, stride=1, relu=False, out
     _check(lib().ssad_grouped_conv3x3_forward(_ptr(x), _ptr(packed), _ptr(bias), N, Cc, H, W, group, stride,
                                               int(relu), _ptr(y), _stream()), "grouped_conv3x3_forward")
     return y
+
+
+def _cg64_geometry(what, Cc, group):
+    """The fp16 grouped 3x3 for 64-wide groups: refused by name, before the library is touched."""
+    if not (isinstance(Cc, int) and isinstance(group, int) and group >= 1 and Cc >= 64 and Cc % 64 == 0
+            and Cc % group == 0 and Cc // group == 64):
+        raise KernelError("%s: %r channels in %r groups (channels a multiple of 64, 64 per group)" % (what, Cc, group))
+
+
+def _f16c(t, name):
+    if t.dtype != torch.float16 or not t.is_contiguous() or not t.is_cuda:
+        raise KernelError("%s must be a contiguous float16 device tensor" % name)
+    return t
+
+
+def grouped_conv3x3_f16_cg64_pack_filter(w, group, out=None):
+    """fp32 [C][64][3][3] -> the fp16 lane-order operands of grouped_conv3x3_f16_cg64 (C * 64 * 9 halves, a
+    permutation of the rounded filter)."""
+    Cc = int(w.shape[0])
+    _cg64_geometry("grouped_conv3x3_f16_cg64_pack_filter", Cc, group)
+    if tuple(w.shape) != (Cc, 64, 3, 3):
+        raise KernelError("grouped_conv3x3_f16_cg64_pack_filter: a %s filter, [C][64][3][3] wanted" % (tuple(w.shape),))
+    _f32c(w, "w")
+    n = Cc * 64 * 9
+    if out is None:
+        out = torch.empty(n, dtype=torch.float16, device="cuda")
+    elif _f16c(out, "out").numel() < n:
+        raise KernelError("grouped_conv3x3_f16_cg64_pack_filter: out holds %d halves, the pack has %d" % (out.numel(), n))
+    _check(lib().ssad_grouped_conv3x3_f16_cg64_pack_filter(_ptr(w), Cc, group, _ptr(out), _stream()),
+           "grouped_conv3x3_f16_cg64_pack_filter")
+    return out
+
+
+def grouped_conv3x3_f16_cg64(x_blocked, packed, bias, C, group, relu=False, out=None):
+    """Grouped 3x3 / stride 1 / pad 1 convolution with 64-wide groups on blocked fp16 [N][C/8][H][W][8]: packed from
+    grouped_conv3x3_f16_cg64_pack_filter, bias fp32 [C] or None; fp32 accumulation, bias + ReLU in the epilogue."""
+    _cg64_geometry("grouped_conv3x3_f16_cg64", C, group)
+    if x_blocked.dim() != 5 or x_blocked.shape[1] != C // 8 or x_blocked.shape[4] != 8:
+        raise KernelError("grouped_conv3x3_f16_cg64: x is %s, blocked [N][%d][H][W][8] wanted"
+                          % (tuple(x_blocked.shape), C // 8))
+    _f16c(x_blocked, "x_blocked"); _f16c(packed, "packed")
+    if packed.numel() < C * 64 * 9:
+        raise KernelError("grouped_conv3x3_f16_cg64: packed holds %d halves, the pack has %d" % (packed.numel(), C * 64 * 9))
+    if bias is not None and _f32c(bias, "bias").numel() != C:
+        raise KernelError("grouped_conv3x3_f16_cg64: bias holds %d values for %d channels" % (bias.numel(), C))
+    N, _, H, W, _ = x_blocked.shape
+    if out is None:
+        out = torch.empty_like(x_blocked)
+    elif _f16c(out, "out").shape != x_blocked.shape:
+        raise KernelError("grouped_conv3x3_f16_cg64: out is %s, x is %s" % (tuple(out.shape), tuple(x_blocked.shape)))
+    _check(lib().ssad_grouped_conv3x3_f16_cg64(_ptr(x_blocked), _ptr(packed), _ptr(bias), N, C, H, W, group, int(relu),
+                                               _ptr(out), _stream()), "grouped_conv3x3_f16_cg64")
+    return out
 
 
 def _grouped_geometry(what, N, Cc, H, W, group, stride):

@@ -31,6 +31,7 @@ GEMM_CONV_SPLIT = 79
 SPLIT_ABSMAX_LEVELS, SPLIT_ABSMAX, GEMM_SPLIT_PACK = 80, 81, 82
 SOFTMAX_FOCAL_FUSED = 83
 GROUPED_DGRAD, GROUPED_WGRAD, GROUPED_PACKS = 84, 85, 86
+GROUPED_F16_CG64, GROUPED_F16_CG64_PACK = 87, 88       # 64-wide groups: the operands of GROUPED_F16 / GROUPED_F16_PACK
 
 # timing classes: one per kernel family.  bound "mfma": work = direct-form FLOPs
 # (2*9*Cout*Cin per output pixel; the Winograd engine executes 1/2.25 of them);
