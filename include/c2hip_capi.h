@@ -110,6 +110,11 @@ C2HIP_CAPI size_t c2hip_net_lowered_ops(c2hip_workspace* ws, const char* name, v
  * lowered operator list as above and a one-line report into report_buf. */
 C2HIP_CAPI size_t c2hip_lower_net(const void* netdef_bytes, size_t n, void* buf, size_t buflen, int* n_ops,
                                   char* report_buf, size_t report_buflen);
+/* The engine the convolution operators run a 3x3 / stride 1 / pad 1 fp32 problem of M output and C input channels
+ * on under `hip_algo` (host logic: the functions of ops/conv3x3_engine.h the operators call).  role 0 = forward,
+ * 1 = data gradient: the pack layout (FilterPackCache::Kind, as its integer); role 2 = filter gradient: 1 on the
+ * split-operand engine, else 0.  -1 for an unknown role. */
+C2HIP_CAPI int c2hip_conv3x3_engine(const char* hip_algo, int role, int M, int C);
 /* Process-wide event counters for tests and benchmarks: "filter_packs" (3x3 filter packs issued by the
  * operators' pack cache), "conv_launch_calls" (3x3 launcher calls made by Conv / ConvGradient / the group
  * operators).  -1 for an unknown name. */

@@ -49,6 +49,8 @@ def load(path=None):
     L.c2hip_net_lowered_ops.argtypes = [vp, cp, vp, sz, C.POINTER(i32)]
     L.c2hip_lower_net.restype = sz
     L.c2hip_lower_net.argtypes = [cp, sz, vp, sz, C.POINTER(i32), cp, sz]
+    L.c2hip_conv3x3_engine.restype = i32
+    L.c2hip_conv3x3_engine.argtypes = [cp, i32, i32, i32]
     L.c2hip_counter.restype = C.c_longlong
     L.c2hip_counter.argtypes = [cp]
     L.c2hip_registered_operators.restype = sz

@@ -210,6 +210,13 @@ def LowerNet(net):
     return _unpack_defs(buf.raw[:need], n_ops.value), rep.value.decode()
 
 
+def Conv3x3Engine(hip_algo, role, M, C):
+    """The 3x3 engine rule of the convolution operators (csrc/ops/conv3x3_engine.h; no workspace, no device).
+    role 0 forward / 1 data gradient -> the FilterPackCache::Kind as an integer; role 2 filter gradient -> 1 on the
+    split-operand engine, else 0."""
+    return int(_capi.load().c2hip_conv3x3_engine(str(hip_algo).encode(), int(role), int(M), int(C)))
+
+
 def Counter(name):
     return int(_capi.load().c2hip_counter(name.encode()))
 

@@ -287,6 +287,13 @@ size_t c2hip_lower_net(const void* netdef_bytes, size_t n, void* buf, size_t buf
   return need;
 }
 
+int c2hip_conv3x3_engine(const char* hip_algo, int role, int M, int C) {
+  const string algo = hip_algo ? hip_algo : "auto";
+  if (role == 2) return SplitFilterGradient(algo, M, C) ? 1 : 0;
+  if (role != 0 && role != 1) return -1;
+  return (int)PackKindOf(PickConv3x3Engine(algo, role == 1 ? C : M), role == 1);
+}
+
 long long c2hip_counter(const char* name) {
   const string n = name ? name : "";
   if (n == "filter_packs") return g_filter_packs_issued.load();

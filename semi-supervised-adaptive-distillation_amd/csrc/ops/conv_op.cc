@@ -26,21 +26,95 @@ bool IsDefaultEngineGeometry(const ConvGeometry& g) {
   return g.order == "NCHW" && g.group >= 1 && g.kernel.size() == 2;
 }
 
-// Algorithm choice, like cuDNN's internal one (conv_op_cudnn.cc:541-558):
-// Winograd F(2x2,3x3) for outputs >= 32 channels wide, the direct kernel
-// otherwise; arg hip_algo = "direct" | "winograd" overrides.
-bool UseWinograd(const string& algo, int out_channels) {
-  if (algo == "direct") return false;
-  if (algo == "winograd") return true;
-  // ("winograd24" names the F(2x4, 3x3) engine the net lowering assigns; wherever it does not apply -- narrow
-  // layers, the filter gradient -- the choice is the automatic one)
-  return out_channels >= 32;
-}
-
 namespace {
 enum { INPUT = 0, FILTER = 1, BIAS = 2, OUTPUT_GRAD = 2 };
 enum { FILTER_GRAD = 0, BIAS_OR_INPUT_GRAD = 1, INPUT_GRAD = 2 };
+
+// problems of equal (outputs, inputs) share launches; classes in order of first appearance
+vector<vector<int>> Classes(const vector<Conv3x3Problem>& probs) {
+  vector<vector<int>> classes;
+  for (int i = 0; i < (int)probs.size(); ++i) {
+    bool placed = false;
+    for (auto& c : classes)
+      if (probs[c[0]].M == probs[i].M && probs[c[0]].C == probs[i].C) { c.push_back(i); placed = true; break; }
+    if (!placed) classes.push_back({i});
+  }
+  return classes;
+}
+
+void CountLaunch(int rc, const char* what) {
+  CAFFE_ENFORCE_EQ(rc, 0, what);
+  ++g_conv_launch_calls;
+}
 }  // namespace
+
+// the packed filter is rebuilt only when the filter blob was written since (ops/filter_pack_cache.h)
+void Conv3x3Runner::FlushPacks(hipStream_t s) {
+  const long long before = cache_.packs_issued();
+  cache_.Flush(s);
+  g_filter_packs_issued += cache_.packs_issued() - before;
+}
+
+const float* Conv3x3Runner::Pack(const Tensor<HIPContext>& filter, FilterPackCache::Kind kind, hipStream_t s) {
+  cache_.Want(filter, kind);
+  FlushPacks(s);
+  return cache_.Packed(filter, kind);
+}
+
+void Conv3x3Runner::Forward(const vector<Conv3x3Problem>& probs, const string& algo, int flags, bool dgrad,
+                            const char* what, hipStream_t s) {
+  auto engine_of = [&](const Conv3x3Problem& p) { return PickConv3x3Engine(algo, dgrad ? p.C : p.M); };
+  for (const Conv3x3Problem& p : probs) cache_.Want(*p.w, PackKindOf(engine_of(p), dgrad));
+  FlushPacks(s);
+  const bool mask = dgrad && (flags & SSAD_CONV_MASK_AUX);
+  for (const vector<int>& cls : Classes(probs)) {
+    const Conv3x3Problem& p0 = probs[cls[0]];
+    const Conv3x3Engine engine = engine_of(p0);
+    const int outs = dgrad ? p0.C : p0.M, ins = dgrad ? p0.M : p0.C;
+    for (size_t at = 0; at < cls.size(); at += SSAD_MAX_CONV_PROBLEMS) {
+      const int n = (int)std::min<size_t>(SSAD_MAX_CONV_PROBLEMS, cls.size() - at);
+      ssad_conv_level lv[SSAD_MAX_CONV_PROBLEMS];
+      for (int j = 0; j < n; ++j) {
+        const Conv3x3Problem& p = probs[cls[at + j]];
+        const float* packed = cache_.Packed(*p.w, PackKindOf(engine, dgrad));
+        lv[j] = dgrad ? ssad_conv_level{p.b->data<float>(), p.y->mutable_data<float>(),
+                                        mask ? p.x->data<float>() : nullptr, p.N, p.H, p.W, packed, nullptr}
+                      : ssad_conv_level{p.x->data<float>(), p.y->mutable_data<float>(), nullptr, p.N, p.H, p.W, packed,
+                                        p.b ? p.b->data<float>() : nullptr};
+      }
+      // per-problem filter / bias (the launchers resolve a problem's own before the launch-wide ones, so one problem
+      // reads the same two pointers either way); the launch-wide bias only says whether one is added at all
+      const float* packed = lv[0].packed;
+      const float* bias = lv[0].bias;
+      CountLaunch(engine == Conv3x3Engine::SPLIT    ? split_.Run(lv, n, packed, bias, outs, ins, flags, s)
+                  : engine == Conv3x3Engine::WINO24 ? ssad_conv3x3_forward_wino24(lv, n, packed, bias, outs, ins, flags, s)
+                  : engine == Conv3x3Engine::WINO   ? ssad_conv3x3_forward_wino(lv, n, packed, bias, outs, ins, flags, s)
+                                                    : ssad_conv3x3_forward(lv, n, packed, bias, outs, ins, flags, s),
+                  what);
+    }
+  }
+}
+
+void Conv3x3Runner::FilterGradient(const vector<Conv3x3Problem>& probs, const vector<int>& mine, float* dW, float* db,
+                                   int M, int C, const string& algo, const char* what, hipStream_t s) {
+  // same contract, same tolerance on either engine, like the native step's SSAD_SPLIT_CONV bit 32
+  const bool split = SplitFilterGradient(algo, M, C);
+  const auto bytes = split ? ssad_conv3x3_wgrad_split_workspace_bytes : ssad_conv3x3_wgrad_workspace_bytes;
+  const auto launch = split ? ssad_conv3x3_wgrad_split : ssad_conv3x3_wgrad;
+  for (size_t at = 0; at < mine.size(); at += SSAD_MAX_LEVELS) {
+    const int n = (int)std::min<size_t>(SSAD_MAX_LEVELS, mine.size() - at);
+    ssad_conv_level lv[SSAD_MAX_LEVELS];
+    for (int j = 0; j < n; ++j) {
+      const Conv3x3Problem& p = probs[mine[at + j]];
+      lv[j] = ssad_conv_level{p.x->data<float>(), nullptr, p.b->data<float>(), p.N, p.H, p.W, nullptr, nullptr};
+    }
+    // the launchers compare the byte count with their need and plan from the problems alone: a workspace that an
+    // earlier, larger launch left behind changes nothing
+    const size_t wsb = bytes(lv, n, M, C);
+    if ((size_t)wgrad_workspace_.size() < wsb) wgrad_workspace_.Resize((TIndex)wsb);
+    CountLaunch(launch(lv, n, dW, db, M, C, at > 0 ? 1 : 0, wgrad_workspace_.mutable_data<uint8_t>(), wsb, s), what);
+  }
+}
 
 template <>
 bool ConvOp<float, HIPContext>::RunDefaultEngine();
@@ -58,10 +132,53 @@ template <>
 bool ConvGradientOp<float, HIPContext>::RunFloat16Pointwise();
 template <>
 bool ConvGradientOp<float, HIPContext>::RunFloat16();
+template <>
+Tensor<HIPContext>* ConvGradientOp<float, HIPContext>::DataGradOutput();
+template <>
+void ConvGradientOp<float, HIPContext>::EmitBiasGrad(const Tensor<HIPContext>& dY, int N, int M, int P);
+template <>
+void ConvGradientOp<float, HIPContext>::EmitFloat16FilterGrads(const Tensor<HIPContext>& filter, int M);
 
 namespace {
 size_t BlockedHalves(int N, int C, int H, int W) {
   return (size_t)N * (size_t)((C + 7) / 8) * 8 * (size_t)H * (size_t)W;
+}
+
+// float16 blobs: what the four routes share.  The fp16 filter as fp32, as the pack kernels read it ...
+const float* FilterAsF32(const Tensor<HIPContext>& filter, Tensor<HIPContext>* scratch, hipStream_t s) {
+  scratch->Resize((TIndex)filter.size());
+  CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(filter.raw_data(), scratch->mutable_data<float>(), filter.size(), s), 0);
+  return scratch->data<float>();
+}
+// ... the fp16 bias [M] as fp32 ...
+const float* BiasAsF32(const Tensor<HIPContext>& b, int M, Tensor<HIPContext>* scratch, hipStream_t s) {
+  CAFFE_ENFORCE(b.IsType<float16>() && b.ndim() == 1 && b.dim32(0) == M);
+  scratch->Resize(M);
+  CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(b.raw_data(), scratch->mutable_data<float>(), M, s), 0);
+  return scratch->data<float>();
+}
+// ... an NCHW fp16 blob channel-blocked ...
+const float* Blocked(const Tensor<HIPContext>& t, int N, int C, int H, int W, Tensor<HIPContext>* scratch, hipStream_t s) {
+  scratch->Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
+  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(t.raw_data(), N, C, H, W, scratch->mutable_data<float>(), s), 0);
+  return scratch->data<float>();
+}
+// ... and the 3x3 fp16 engine into an NCHW fp16 blob `out` of `outs` channels: channel-blocked, then unblocked; a
+// width that is not a multiple of 8 (bbox_pred: 36) leaves through NCHW fp32.
+void Conv3x3F16IntoBlob(const float* xb, const float* packed, const float* bias, int N, int ins, int H, int W, int outs,
+                        int flags, Tensor<HIPContext>* scratch, void* out, const char* what, hipStream_t s) {
+  if (outs % 8 == 0) {
+    scratch->Resize((TIndex)((BlockedHalves(N, outs, H, W) + 1) / 2));
+    CAFFE_ENFORCE_EQ(ssad_conv3x3_forward_f16(xb, packed, bias, nullptr, N, ins, H, W, outs, flags,
+                                              scratch->mutable_data<float>(), s), 0, what);
+    CAFFE_ENFORCE_EQ(ssad_f16_unblock_activations(scratch->data<float>(), N, outs, H, W, out, s), 0);
+  } else {
+    const size_t n = (size_t)N * outs * H * W;
+    scratch->Resize((TIndex)n);
+    CAFFE_ENFORCE_EQ(ssad_conv3x3_forward_f16(xb, packed, bias, nullptr, N, ins, H, W, outs,
+                                              flags | SSAD_F16_OUT_NCHW_F32, scratch->mutable_data<float>(), s), 0, what);
+    CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(scratch->data<float>(), out, n, s), 0);
+  }
 }
 
 // hip_algo = "grouped" is a request, not a hint: the geometry of kernels/grouped_conv3x3.hip / grouped_conv3x3_grad.hip
@@ -85,6 +202,23 @@ void EnforceGroupedGeometry(const char* op, const ConvGeometry& g, int N, int C,
 }  // namespace
 
 template <>
+Tensor<HIPContext>* ConvGradientOp<float, HIPContext>::DataGradOutput() {
+  if (OutputSize() != 3 && !(no_bias_ && OutputSize() == 2)) return nullptr;
+  auto* dX = Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD);
+  dX->ResizeLike(Input(INPUT));
+  return dX;
+}
+
+template <>
+void ConvGradientOp<float, HIPContext>::EmitBiasGrad(const Tensor<HIPContext>& dY, int N, int M, int P) {
+  if (no_bias_) return;
+  auto* dbias = Output(BIAS_OR_INPUT_GRAD);
+  dbias->Resize(M);
+  CAFFE_ENFORCE_EQ(ssad_channel_sum(dY.data<float>(), N, M, P, dbias->mutable_data<float>(), 0,
+                                    context_.hip_stream()), 0);
+}
+
+template <>
 bool ConvOp<float, HIPContext>::RunOnDevice() {
   auto& X = Input(INPUT);
   auto& filter = Input(FILTER);
@@ -103,40 +237,18 @@ bool ConvOp<float, HIPContext>::RunOnDevice() {
                 "Convolution op: input channels does not match: # of input channels ", C,
                 " is not equal to kernel channels * group:", filter.dim32(1), "*", geom_.group);
   CAFFE_ENFORCE(filter.dim32(2) == geom_.kernel[0] && filter.dim32(3) == geom_.kernel[1]);
-  const float* bias = nullptr;
+  const Tensor<HIPContext>* bias = nullptr;
   if (InputSize() == 3) {
-    auto& b = Input(BIAS);
-    CAFFE_ENFORCE(b.ndim() == 1);
-    CAFFE_ENFORCE(b.dim32(0) == M);
-    bias = b.data<float>();
+    bias = &Input(BIAS);
+    CAFFE_ENFORCE(bias->ndim() == 1);
+    CAFFE_ENFORCE(bias->dim32(0) == M);
   }
   if (algo_ == "grouped") return RunGrouped();
   if (!IsSubnetGeometry(geom_)) return RunDefaultEngine();
   Y->Resize(N, M, H, W);   // 3x3 / s1 / p1 keeps the spatial size
-
-  hipStream_t s = context_.hip_stream();
-  ssad_conv_level lv{X.data<float>(), Y->mutable_data<float>(), nullptr, N, H, W, nullptr, nullptr};
   const int flags = (fuse_relu_ ? SSAD_CONV_RELU : 0) | (fuse_sigmoid_ ? SSAD_CONV_SIGMOID : 0);
-  int rc;
-  // the packed filter is rebuilt only when the filter blob was written since (ops/filter_pack_cache.h)
-  // "split" / "winograd24" are assigned by the net lowering (net_lowering.cc): the split-operand engine from 256
-  // outputs up, F(2x4) from 128
-  const bool sp = algo_ == "split" && M >= 256;
-  const bool f24 = (algo_ == "winograd24" || algo_ == "split") && M >= 128 && !sp;
-  const bool wino = UseWinograd((algo_ == "winograd24" || algo_ == "split") ? string("auto") : algo_, M);
-  const auto kind = sp ? FilterPackCache::SPLIT_FWD : f24 ? FilterPackCache::WINO24_FWD
-                       : wino ? FilterPackCache::WINO_FWD : FilterPackCache::DIRECT_FWD;
-  const long long before = pack_cache_.packs_issued();
-  pack_cache_.Want(filter, kind);
-  pack_cache_.Flush(s);
-  g_filter_packs_issued += pack_cache_.packs_issued() - before;
-  const float* packed = pack_cache_.Packed(filter, kind);
-  rc = sp ? split_.Run(&lv, 1, packed, bias, M, C, flags, s)
-       : f24 ? ssad_conv3x3_forward_wino24(&lv, 1, packed, bias, M, C, flags, s)
-       : wino ? ssad_conv3x3_forward_wino(&lv, 1, packed, bias, M, C, flags, s)
-              : ssad_conv3x3_forward(&lv, 1, packed, bias, M, C, flags, s);
-  CAFFE_ENFORCE_EQ(rc, 0, "Conv launch failed");
-  ++g_conv_launch_calls;
+  runner_.Forward({Conv3x3Problem(X, filter, bias, Y)}, algo_, flags, false, "Conv launch failed",
+                  context_.hip_stream());
   return true;
 }
 
@@ -152,11 +264,7 @@ bool ConvOp<float, HIPContext>::RunGrouped() {
   const int st = geom_.stride[0];
   Y->Resize(N, M, (H - 1) / st + 1, (W - 1) / st + 1);
   hipStream_t s = context_.hip_stream();
-  const long long before = pack_cache_.packs_issued();
-  pack_cache_.Want(filter, FilterPackCache::GROUPED_FWD);
-  pack_cache_.Flush(s);
-  g_filter_packs_issued += pack_cache_.packs_issued() - before;
-  const int rc = ssad_grouped_conv3x3_forward(X.data<float>(), pack_cache_.Packed(filter, FilterPackCache::GROUPED_FWD),
+  const int rc = ssad_grouped_conv3x3_forward(X.data<float>(), runner_.Pack(filter, FilterPackCache::GROUPED_FWD, s),
                                               InputSize() == 3 ? Input(BIAS).data<float>() : nullptr, N, C, H, W,
                                               geom_.group, st, fuse_relu_ ? 1 : 0, Y->mutable_data<float>(), s);
   CAFFE_ENFORCE_EQ(rc, 0, "Conv(hip_algo=grouped) launch failed: ", GroupedGeometryText(geom_, N, C, M, H, W));
@@ -189,19 +297,9 @@ bool ConvGradientOp<float, HIPContext>::RunGrouped() {
   CAFFE_ENFORCE_EQ(rc, 0, "ConvGradient(hip_algo=grouped) filter launch failed: ",
                    GroupedGeometryText(geom_, N, C, M, H, W));
   ++g_conv_launch_calls;
-  if (!no_bias_) {
-    auto* dbias = Output(BIAS_OR_INPUT_GRAD);
-    dbias->Resize(M);
-    CAFFE_ENFORCE_EQ(ssad_channel_sum(dY.data<float>(), N, M, OH * OW, dbias->mutable_data<float>(), 0, s), 0);
-  }
-  if (OutputSize() == 3 || (no_bias_ && OutputSize() == 2)) {
-    auto* dX = Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD);
-    dX->ResizeLike(X);
-    const long long before = pack_cache_.packs_issued();
-    pack_cache_.Want(filter, FilterPackCache::GROUPED_DGRAD);
-    pack_cache_.Flush(s);
-    g_filter_packs_issued += pack_cache_.packs_issued() - before;
-    rc = ssad_grouped_conv3x3_dgrad(dY.data<float>(), pack_cache_.Packed(filter, FilterPackCache::GROUPED_DGRAD),
+  EmitBiasGrad(dY, N, M, OH * OW);
+  if (auto* dX = DataGradOutput()) {
+    rc = ssad_grouped_conv3x3_dgrad(dY.data<float>(), runner_.Pack(filter, FilterPackCache::GROUPED_DGRAD, s),
                                     relu_grad_on_input_ ? X.data<float>() : nullptr, N, C, H, W, geom_.group, st,
                                     dX->mutable_data<float>(), s);
     CAFFE_ENFORCE_EQ(rc, 0, "ConvGradient(hip_algo=grouped) data launch failed: ",
@@ -214,9 +312,13 @@ bool ConvGradientOp<float, HIPContext>::RunGrouped() {
 // A pointwise layer the GEMM kernels take: 1x1, no padding, no dilation, equal strides, one group,
 // 16-byte pixel rows, 16-byte aligned channel rows (C % 4), tensors below 2 GiB.
 // SSAD_CONV1X1_ENGINE=blas keeps the im2col + general-GEMM route (kernels/gemm_general.hip).
+static bool BlasRouteForced() {
+  static const bool on = [] { const char* e = getenv("SSAD_CONV1X1_ENGINE"); return e && std::string(e) == "blas"; }();
+  return on;
+}
+
 static bool PointwiseGemmEligible(const ConvGeometry& g, int N, int C, int M, int P) {
-  static const bool off = [] { const char* e = getenv("SSAD_CONV1X1_ENGINE"); return e && std::string(e) == "blas"; }();
-  if (off) return false;
+  if (BlasRouteForced()) return false;
   if (g.kernel[0] != 1 || g.kernel[1] != 1 || g.group != 1) return false;
   if (g.pads != vector<int>{0, 0, 0, 0} || g.dilation != vector<int>{1, 1}) return false;
   if (g.stride[0] != g.stride[1] || g.stride[0] < 1) return false;
@@ -228,11 +330,7 @@ static bool PointwiseGemmEligible(const ConvGeometry& g, int N, int C, int M, in
 // A k x k layer (any stride / pad, one group, square kernel, no dilation) the implicit-GEMM kernel
 // takes: any output map size, tensors below 2 GiB.  SSAD_CONV1X1_ENGINE=blas disables it too.
 static bool ImplicitGemmEligible(const ConvGeometry& g, int N, int C, int H, int W, int M, int P) {
-  static const bool off = [] {
-    const char* e = getenv("SSAD_CONV1X1_ENGINE");
-    return e && std::string(e) == "blas";
-  }();
-  if (off || g.group != 1 || g.kernel[0] != g.kernel[1] || g.dilation != vector<int>{1, 1}) return false;
+  if (BlasRouteForced() || g.group != 1 || g.kernel[0] != g.kernel[1] || g.dilation != vector<int>{1, 1}) return false;
   if (g.stride[0] != g.stride[1] || g.stride[0] < 1) return false;
   if (g.pads[0] != g.pads[1] || g.pads[0] != g.pads[2] || g.pads[0] != g.pads[3]) return false;
   if (N < 1) return false;
@@ -352,9 +450,7 @@ bool ConvGradientOp<float, HIPContext>::RunDefaultEngine() {
   const int K = C * kh * kw, P = OH * OW, Kg = K / G, Mg = M / G;
   const bool pointwise = kh == 1 && kw == 1 && geom_.stride == vector<int>{1, 1} &&
                          geom_.pads == vector<int>{0, 0, 0, 0};
-  const bool want_dx = OutputSize() == 3 || (no_bias_ && OutputSize() == 2);
-  Tensor<HIPContext>* dX = want_dx ? Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD) : nullptr;
-  if (dX) dX->ResizeLike(X);
+  Tensor<HIPContext>* dX = DataGradOutput();
   if (PointwiseGemmEligible(geom_, N, C, M, P) && P % 16 == 0) {
     // dfilter = sum_{n,p} dY X^T (split reduction), dX = filter^T . dY on the GEMM kernels
     const int st = geom_.stride[0];
@@ -377,14 +473,7 @@ bool ConvGradientOp<float, HIPContext>::RunDefaultEngine() {
       if (st > 1)
         CAFFE_ENFORCE_EQ(ssad_subsample_grad(dxs, N, C, H, W, st, 0, dX->mutable_data<float>(), s), 0);
     }
-    if (!no_bias_) {
-      auto* dbias = Output(BIAS_OR_INPUT_GRAD);
-      dbias->Resize(M);
-      CAFFE_ENFORCE_EQ(ssad_channel_sum(dY.data<float>(), N, M, P, dbias->mutable_data<float>(), 0, s), 0);
-    }
-    return true;
-  }
-  {
+  } else {
     // k x k / strided layers of group 1 (FPN's P6 / P7, the stem): the whole batch at once -- im2col with the batch
     // flattened into the GEMM's column index, filter gradient on the nt GEMM kernel (deterministic split
     // reduction), data gradient = nn GEMM + gather-form col2im (kernels/conv_strided.hip).  The per-image loop
@@ -439,55 +528,46 @@ bool ConvGradientOp<float, HIPContext>::RunDefaultEngine() {
                            "ConvGradient (input, batched col2im) launch failed");
         }
       }
-      if (!no_bias_) {
-        auto* dbias = Output(BIAS_OR_INPUT_GRAD);
-        dbias->Resize(M);
-        CAFFE_ENFORCE_EQ(ssad_channel_sum(dY.data<float>(), N, M, P, dbias->mutable_data<float>(), 0, s), 0);
+    } else {
+      if (!pointwise) col_buffer_.Resize((TIndex)K * P);
+      for (int n = 0; n < N; ++n) {
+        const float* xn = X.data<float>() + (size_t)n * C * H * W;
+        const float* dyn = dY.data<float>() + (size_t)n * M * P;
+        const float* col = xn;
+        if (!pointwise) {
+          float* cb = col_buffer_.mutable_data<float>();
+          CAFFE_ENFORCE_EQ(ssad_im2col(xn, C, H, W, kh, kw, geom_.dilation[0], geom_.dilation[1],
+                                       geom_.pads[0], geom_.pads[1], geom_.pads[2], geom_.pads[3],
+                                       geom_.stride[0], geom_.stride[1], cb, s), 0);
+          col = cb;
+        }
+        // dfilter[M][K] (+)= dY[n][M][P] . col[K][P]^T
+        if (G == 1)
+          GemmRowMajor(s, false, true, M, K, P, 1.0f, dyn, P, col, P, n == 0 ? 0.0f : 1.0f,
+                       dfilter->mutable_data<float>(), K);
+        else   // per group: dfilter[g][Mg][Kg] (+)= dY[n][g][Mg][P] . col[g][Kg][P]^T
+          GemmRowMajorStridedBatched(s, false, true, Mg, Kg, P, 1.0f, dyn, P, (long long)Mg * P, col, P,
+                                     (long long)Kg * P, n == 0 ? 0.0f : 1.0f,
+                                     dfilter->mutable_data<float>(), Kg, (long long)Mg * Kg, G);
+        if (dX) {
+          float* dxn = dX->mutable_data<float>() + (size_t)n * C * H * W;
+          float* dcol = pointwise ? dxn : col_buffer_.mutable_data<float>();
+          // dcol[K][P] = filter[M][K]^T . dY[n][M][P]
+          if (G == 1)
+            GemmRowMajor(s, true, false, K, P, M, 1.0f, filter.data<float>(), K, dyn, P, 0.0f, dcol, P);
+          else   // per group: dcol[g][Kg][P] = filter[g][Mg][Kg]^T . dY[n][g][Mg][P]
+            GemmRowMajorStridedBatched(s, true, false, Kg, P, Mg, 1.0f, filter.data<float>(), Kg,
+                                       (long long)Mg * Kg, dyn, P, (long long)Mg * P, 0.0f, dcol, P,
+                                       (long long)Kg * P, G);
+          if (!pointwise)
+            CAFFE_ENFORCE_EQ(ssad_col2im(dcol, C, H, W, kh, kw, geom_.dilation[0], geom_.dilation[1],
+                                         geom_.pads[0], geom_.pads[1], geom_.pads[2], geom_.pads[3],
+                                         geom_.stride[0], geom_.stride[1], dxn, s), 0);
+        }
       }
-      return true;
     }
   }
-  if (!pointwise) col_buffer_.Resize((TIndex)K * P);
-  for (int n = 0; n < N; ++n) {
-    const float* xn = X.data<float>() + (size_t)n * C * H * W;
-    const float* dyn = dY.data<float>() + (size_t)n * M * P;
-    const float* col = xn;
-    if (!pointwise) {
-      float* cb = col_buffer_.mutable_data<float>();
-      CAFFE_ENFORCE_EQ(ssad_im2col(xn, C, H, W, kh, kw, geom_.dilation[0], geom_.dilation[1],
-                                   geom_.pads[0], geom_.pads[1], geom_.pads[2], geom_.pads[3],
-                                   geom_.stride[0], geom_.stride[1], cb, s), 0);
-      col = cb;
-    }
-    // dfilter[M][K] (+)= dY[n][M][P] . col[K][P]^T
-    if (G == 1)
-      GemmRowMajor(s, false, true, M, K, P, 1.0f, dyn, P, col, P, n == 0 ? 0.0f : 1.0f,
-                   dfilter->mutable_data<float>(), K);
-    else   // per group: dfilter[g][Mg][Kg] (+)= dY[n][g][Mg][P] . col[g][Kg][P]^T
-      GemmRowMajorStridedBatched(s, false, true, Mg, Kg, P, 1.0f, dyn, P, (long long)Mg * P, col, P,
-                                 (long long)Kg * P, n == 0 ? 0.0f : 1.0f,
-                                 dfilter->mutable_data<float>(), Kg, (long long)Mg * Kg, G);
-    if (dX) {
-      float* dxn = dX->mutable_data<float>() + (size_t)n * C * H * W;
-      float* dcol = pointwise ? dxn : col_buffer_.mutable_data<float>();
-      // dcol[K][P] = filter[M][K]^T . dY[n][M][P]
-      if (G == 1)
-        GemmRowMajor(s, true, false, K, P, M, 1.0f, filter.data<float>(), K, dyn, P, 0.0f, dcol, P);
-      else   // per group: dcol[g][Kg][P] = filter[g][Mg][Kg]^T . dY[n][g][Mg][P]
-        GemmRowMajorStridedBatched(s, true, false, Kg, P, Mg, 1.0f, filter.data<float>(), Kg,
-                                   (long long)Mg * Kg, dyn, P, (long long)Mg * P, 0.0f, dcol, P,
-                                   (long long)Kg * P, G);
-      if (!pointwise)
-        CAFFE_ENFORCE_EQ(ssad_col2im(dcol, C, H, W, kh, kw, geom_.dilation[0], geom_.dilation[1],
-                                     geom_.pads[0], geom_.pads[1], geom_.pads[2], geom_.pads[3],
-                                     geom_.stride[0], geom_.stride[1], dxn, s), 0);
-    }
-  }
-  if (!no_bias_) {
-    auto* dbias = Output(BIAS_OR_INPUT_GRAD);
-    dbias->Resize(M);
-    CAFFE_ENFORCE_EQ(ssad_channel_sum(dY.data<float>(), N, M, P, dbias->mutable_data<float>(), 0, s), 0);
-  }
+  EmitBiasGrad(dY, N, M, P);
   return true;
 }
 
@@ -518,42 +598,14 @@ bool ConvGradientOp<float, HIPContext>::RunOnDevice() {
     db = dbias->mutable_data<float>();
   }
   hipStream_t s = context_.hip_stream();
-
-  // filter (+ bias) gradient: overwrite, beta = 0 (conv_op_cudnn.cc:1037)
-  ssad_conv_level wl{X.data<float>(), nullptr, dY.data<float>(), N, H, W, nullptr, nullptr};
-  // hip_algo = "split": the >= 128-wide filter gradients on the split-operand engine (conv3x3_wgrad_split.hip)
-  const bool wsplit = algo_ == "split" && M >= 128 && C >= 64;
-  const size_t wsb = wsplit ? ssad_conv3x3_wgrad_split_workspace_bytes(&wl, 1, M, C)
-                            : ssad_conv3x3_wgrad_workspace_bytes(&wl, 1, M, C);
-  workspace_.Resize((TIndex)wsb);
-  int rc = (wsplit ? ssad_conv3x3_wgrad_split : ssad_conv3x3_wgrad)(&wl, 1, dfilter->mutable_data<float>(), db, M, C, 0,
-                                                                     workspace_.mutable_data<uint8_t>(), wsb, s);
-  CAFFE_ENFORCE_EQ(rc, 0, "ConvGradient (filter) launch failed");
-  ++g_conv_launch_calls;
-
-  if (OutputSize() == 3 || (no_bias_ && OutputSize() == 2)) {
-    auto* dX = Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD);
-    dX->ResizeLike(X);
-    ssad_conv_level dl{dY.data<float>(), dX->mutable_data<float>(),
-                       relu_grad_on_input_ ? X.data<float>() : nullptr, N, H, W, nullptr, nullptr};
-    const int flags = relu_grad_on_input_ ? SSAD_CONV_MASK_AUX : 0;
-    const bool sp = algo_ == "split" && C >= 256;            // trained nets (net_lowering.cc)
-    const bool f24 = (algo_ == "winograd24" || algo_ == "split") && C >= 128 && !sp;
-    const bool wino = UseWinograd(algo_, C);      // the data gradient has C output channels
-    const auto kind = sp ? FilterPackCache::SPLIT_DGRAD : f24 ? FilterPackCache::WINO24_DGRAD
-                         : wino ? FilterPackCache::WINO_DGRAD : FilterPackCache::DIRECT_DGRAD;
-    const long long before = pack_cache_.packs_issued();
-    pack_cache_.Want(filter, kind);
-    pack_cache_.Flush(s);
-    g_filter_packs_issued += pack_cache_.packs_issued() - before;
-    const float* packed = pack_cache_.Packed(filter, kind);
-    rc = sp ? split_.Run(&dl, 1, packed, nullptr, C, M, flags, s)
-         : f24 ? ssad_conv3x3_forward_wino24(&dl, 1, packed, nullptr, C, M, flags, s)
-         : wino ? ssad_conv3x3_forward_wino(&dl, 1, packed, nullptr, C, M, flags, s)
-                : ssad_conv3x3_forward(&dl, 1, packed, nullptr, C, M, flags, s);
-    CAFFE_ENFORCE_EQ(rc, 0, "ConvGradient (data) launch failed");
-    ++g_conv_launch_calls;
-  }
+  // one problem and one filter: the filter (+ bias) gradient, then the data gradient
+  auto* dX = DataGradOutput();
+  const vector<Conv3x3Problem> one{Conv3x3Problem(X, filter, &dY, dX)};
+  runner_.FilterGradient(one, {0}, dfilter->mutable_data<float>(), db, M, C, algo_, "ConvGradient (filter) launch failed",
+                         s);
+  if (dX)
+    runner_.Forward(one, algo_, relu_grad_on_input_ ? SSAD_CONV_MASK_AUX : 0, true, "ConvGradient (data) launch failed",
+                    s);
   return true;
 }
 
@@ -575,42 +627,16 @@ bool ConvOp<float, HIPContext>::RunFloat16() {
   CAFFE_ENFORCE(C == filter.dim32(1) && filter.dim32(2) == 3 && filter.dim32(3) == 3);
   hipStream_t s = context_.hip_stream();
   // filter: fp16 [M][C][3][3] -> fp32 -> packed fp16; bias -> fp32
-  auto& wf32 = f16_scratch_[0];
-  wf32.Resize((TIndex)filter.size());
-  CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(filter.raw_data(), wf32.mutable_data<float>(), filter.size(), s), 0);
+  const float* wf32 = FilterAsF32(filter, &filter_f32_, s);
   packed_filter_.Resize((TIndex)((ssad_f16_filter_halves(M, C) + 1) / 2));
   float* packed = packed_filter_.mutable_data<float>();
-  CAFFE_ENFORCE_EQ(ssad_f16_pack_filter(wf32.data<float>(), M, C, packed, nullptr, s), 0);
-  const float* bias = nullptr;
-  if (InputSize() == 3) {
-    auto& b = Input(BIAS);
-    CAFFE_ENFORCE(b.IsType<float16>() && b.ndim() == 1 && b.dim32(0) == M);
-    auto& b32 = f16_scratch_[1];
-    b32.Resize(M);
-    CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(b.raw_data(), b32.mutable_data<float>(), M, s), 0);
-    bias = b32.data<float>();
-  }
+  CAFFE_ENFORCE_EQ(ssad_f16_pack_filter(wf32, M, C, packed, nullptr, s), 0);
+  const float* bias = InputSize() == 3 ? BiasAsF32(Input(BIAS), M, &bias_f32_, s) : nullptr;
   // activations: NCHW fp16 -> channel-blocked -> convolution -> NCHW fp16
-  auto& xb = f16_scratch_[2];
-  xb.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
-  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(X.raw_data(), N, C, H, W, xb.mutable_data<float>(), s), 0);
+  const float* xb = Blocked(X, N, C, H, W, &x_blocked_, s);
   Y->Resize(N, M, H, W);
-  void* y = Y->raw_mutable_data(TypeMeta::Make<float16>());
-  const int flags = fuse_relu_ ? SSAD_CONV_RELU : 0;
-  if (M % 8 == 0) {
-    auto& yb = f16_scratch_[3];
-    yb.Resize((TIndex)((BlockedHalves(N, M, H, W) + 1) / 2));
-    CAFFE_ENFORCE_EQ(ssad_conv3x3_forward_f16(xb.data<float>(), packed, bias, nullptr, N, C, H, W, M, flags,
-                                              yb.mutable_data<float>(), s), 0, "float16 Conv launch failed");
-    CAFFE_ENFORCE_EQ(ssad_f16_unblock_activations(yb.data<float>(), N, M, H, W, y, s), 0);
-  } else {   // an output width that is not a multiple of 8 (bbox_pred: 36) leaves through fp32
-    auto& y32 = f16_scratch_[3];
-    y32.Resize((TIndex)Y->size());
-    CAFFE_ENFORCE_EQ(ssad_conv3x3_forward_f16(xb.data<float>(), packed, bias, nullptr, N, C, H, W, M,
-                                              flags | SSAD_F16_OUT_NCHW_F32, y32.mutable_data<float>(), s),
-                     0, "float16 Conv launch failed");
-    CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(y32.data<float>(), y, Y->size(), s), 0);
-  }
+  Conv3x3F16IntoBlob(xb, packed, bias, N, C, H, W, M, fuse_relu_ ? SSAD_CONV_RELU : 0, &out_blocked_,
+                     Y->raw_mutable_data(TypeMeta::Make<float16>()), "float16 Conv launch failed", s);
   return true;
 }
 
@@ -620,7 +646,6 @@ bool ConvGradientOp<float, HIPContext>::RunFloat16() {
   auto& X = Input(INPUT);
   auto& filter = Input(FILTER);
   auto& dY = Input(OUTPUT_GRAD);
-  auto* dfilter = Output(FILTER_GRAD);
   if (IsPointwiseF16Geometry(geom_)) return RunFloat16Pointwise();
   CAFFE_ENFORCE(IsSubnetGeometry(geom_),
                 "float16 ConvGradient: the HIP engines implement kernel 3 / stride 1 / pad 1 and kernel 1 / "
@@ -635,59 +660,41 @@ bool ConvGradientOp<float, HIPContext>::RunFloat16() {
                     dY.dim32(3) == W,
                 "output gradient shape does not match the convolution output");
   hipStream_t s = context_.hip_stream();
-  auto& xb = f16_scratch_[0];
-  auto& dyb = f16_scratch_[1];
-  xb.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
-  dyb.Resize((TIndex)((BlockedHalves(N, M, H, W) + 1) / 2));
-  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(X.raw_data(), N, C, H, W, xb.mutable_data<float>(), s), 0);
-  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(dY.raw_data(), N, M, H, W, dyb.mutable_data<float>(), s), 0);
+  const float* xb = Blocked(X, N, C, H, W, &x_blocked_, s);
+  const float* dyb = Blocked(dY, N, M, H, W, &dy_blocked_, s);
   // filter / bias gradient in fp32, stored as fp16 (conv_op_cudnn.cc:1037: overwrite)
-  auto& dw32 = f16_scratch_[2];
-  auto& db32 = f16_scratch_[3];
-  dw32.Resize((TIndex)filter.size());
-  db32.Resize(M);
+  dfilter_f32_.Resize((TIndex)filter.size());
+  dbias_f32_.Resize(M);
   const size_t wsb = ssad_conv3x3_wgrad_f16_workspace_bytes(N, C, H, W, M);
   workspace_.Resize((TIndex)wsb);
-  CAFFE_ENFORCE_EQ(ssad_conv3x3_wgrad_f16(xb.data<float>(), dyb.data<float>(), N, C, H, W, M, 0, 1.0f,
-                                          dw32.mutable_data<float>(),
-                                          no_bias_ ? nullptr : db32.mutable_data<float>(),
+  CAFFE_ENFORCE_EQ(ssad_conv3x3_wgrad_f16(xb, dyb, N, C, H, W, M, 0, 1.0f, dfilter_f32_.mutable_data<float>(),
+                                          no_bias_ ? nullptr : dbias_f32_.mutable_data<float>(),
                                           workspace_.mutable_data<uint8_t>(), wsb, s),
                    0, "float16 ConvGradient (filter) launch failed");
-  dfilter->ResizeLike(filter);
-  CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(dw32.data<float>(), dfilter->raw_mutable_data(TypeMeta::Make<float16>()),
-                                        filter.size(), s), 0);
-  if (!no_bias_) {
-    auto* dbias = Output(BIAS_OR_INPUT_GRAD);
-    dbias->Resize(M);
-    CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(db32.data<float>(), dbias->raw_mutable_data(TypeMeta::Make<float16>()),
-                                          M, s), 0);
-  }
-  if (OutputSize() == 3 || (no_bias_ && OutputSize() == 2)) {
-    auto* dX = Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD);
-    dX->ResizeLike(X);
-    auto& wf32 = f16_scratch_[4];
-    wf32.Resize((TIndex)filter.size());
-    CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(filter.raw_data(), wf32.mutable_data<float>(), filter.size(), s), 0);
+  EmitFloat16FilterGrads(filter, M);
+  if (auto* dX = DataGradOutput()) {
+    const float* wf32 = FilterAsF32(filter, &filter_f32_, s);
     packed_filter_.Resize((TIndex)((ssad_f16_filter_halves(M, C) + 1) / 2));
     float* packed = packed_filter_.mutable_data<float>();
-    CAFFE_ENFORCE_EQ(ssad_f16_pack_filter(wf32.data<float>(), M, C, nullptr, packed, s), 0);
-    void* dx = dX->raw_mutable_data(TypeMeta::Make<float16>());
-    auto& out = f16_scratch_[5];
-    if (C % 8 == 0) {
-      out.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
-      CAFFE_ENFORCE_EQ(ssad_conv3x3_forward_f16(dyb.data<float>(), packed, nullptr, nullptr, N, M, H, W, C, 0,
-                                                out.mutable_data<float>(), s), 0,
-                       "float16 ConvGradient (data) launch failed");
-      CAFFE_ENFORCE_EQ(ssad_f16_unblock_activations(out.data<float>(), N, C, H, W, dx, s), 0);
-    } else {
-      out.Resize((TIndex)X.size());
-      CAFFE_ENFORCE_EQ(ssad_conv3x3_forward_f16(dyb.data<float>(), packed, nullptr, nullptr, N, M, H, W, C,
-                                                SSAD_F16_OUT_NCHW_F32, out.mutable_data<float>(), s), 0,
-                       "float16 ConvGradient (data) launch failed");
-      CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(out.data<float>(), dx, X.size(), s), 0);
-    }
+    CAFFE_ENFORCE_EQ(ssad_f16_pack_filter(wf32, M, C, nullptr, packed, s), 0);
+    Conv3x3F16IntoBlob(dyb, packed, nullptr, N, M, H, W, C, 0, &out_blocked_,
+                       dX->raw_mutable_data(TypeMeta::Make<float16>()), "float16 ConvGradient (data) launch failed", s);
   }
   return true;
+}
+
+template <>
+void ConvGradientOp<float, HIPContext>::EmitFloat16FilterGrads(const Tensor<HIPContext>& filter, int M) {
+  hipStream_t s = context_.hip_stream();
+  auto* dfilter = Output(FILTER_GRAD);
+  dfilter->ResizeLike(filter);
+  CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(dfilter_f32_.data<float>(), dfilter->raw_mutable_data(TypeMeta::Make<float16>()),
+                                        filter.size(), s), 0);
+  if (no_bias_) return;
+  auto* dbias = Output(BIAS_OR_INPUT_GRAD);
+  dbias->Resize(M);
+  CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(dbias_f32_.data<float>(), dbias->raw_mutable_data(TypeMeta::Make<float16>()), M,
+                                        s), 0);
 }
 
 // float16 blobs, pointwise layer (the backbones' 1x1 convolutions under CudnnConvOp<float16>,
@@ -706,31 +713,18 @@ bool ConvOp<float, HIPContext>::RunFloat16Pointwise() {
   CAFFE_ENFORCE(M % 8 == 0, "float16 pointwise Conv: the output width must be a multiple of 8 channels");
   const int OH = (H - 1) / st + 1, OW = (W - 1) / st + 1;
   hipStream_t s = context_.hip_stream();
-  auto& wf32 = f16_scratch_[0];
-  wf32.Resize((TIndex)filter.size());
-  CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(filter.raw_data(), wf32.mutable_data<float>(), filter.size(), s), 0);
+  const float* wf32 = FilterAsF32(filter, &filter_f32_, s);
   packed_filter_.Resize((TIndex)((ssad_pw_f16_filter_halves(M, C) + 1) / 2));
   float* packed = packed_filter_.mutable_data<float>();
-  CAFFE_ENFORCE_EQ(ssad_pw_f16_pack_filter(wf32.data<float>(), M, C, packed, nullptr, s), 0);
-  const float* bias = nullptr;
-  if (InputSize() == 3) {
-    auto& b = Input(BIAS);
-    CAFFE_ENFORCE(b.IsType<float16>() && b.ndim() == 1 && b.dim32(0) == M);
-    auto& b32 = f16_scratch_[1];
-    b32.Resize(M);
-    CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(b.raw_data(), b32.mutable_data<float>(), M, s), 0);
-    bias = b32.data<float>();
-  }
-  auto& xb = f16_scratch_[2];
-  auto& yb = f16_scratch_[3];
-  xb.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
-  yb.Resize((TIndex)((BlockedHalves(N, M, OH, OW) + 1) / 2));
-  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(X.raw_data(), N, C, H, W, xb.mutable_data<float>(), s), 0);
-  const ssad_pw_f16 d{xb.data<float>(), packed, bias, nullptr, nullptr, yb.mutable_data<float>(),
+  CAFFE_ENFORCE_EQ(ssad_pw_f16_pack_filter(wf32, M, C, packed, nullptr, s), 0);
+  const float* bias = InputSize() == 3 ? BiasAsF32(Input(BIAS), M, &bias_f32_, s) : nullptr;
+  const float* xb = Blocked(X, N, C, H, W, &x_blocked_, s);
+  out_blocked_.Resize((TIndex)((BlockedHalves(N, M, OH, OW) + 1) / 2));
+  const ssad_pw_f16 d{xb, packed, bias, nullptr, nullptr, out_blocked_.mutable_data<float>(),
                       N, C, M, OH, OW, H, W, st, fuse_relu_ ? SSAD_CONV_RELU : 0};
   CAFFE_ENFORCE_EQ(ssad_conv1x1_f16(&d, s), 0, "float16 pointwise Conv launch failed");
   Y->Resize(N, M, OH, OW);
-  CAFFE_ENFORCE_EQ(ssad_f16_unblock_activations(yb.data<float>(), N, M, OH, OW,
+  CAFFE_ENFORCE_EQ(ssad_f16_unblock_activations(out_blocked_.data<float>(), N, M, OH, OW,
                                                 Y->raw_mutable_data(TypeMeta::Make<float16>()), s), 0);
   return true;
 }
@@ -743,7 +737,6 @@ bool ConvGradientOp<float, HIPContext>::RunFloat16Pointwise() {
   auto& X = Input(INPUT);
   auto& filter = Input(FILTER);
   auto& dY = Input(OUTPUT_GRAD);
-  auto* dfilter = Output(FILTER_GRAD);
   CAFFE_ENFORCE(filter.IsType<float16>() && dY.IsType<float16>(),
                 "float16 ConvGradient: filter and output gradient must be float16 too");
   CAFFE_ENFORCE(!relu_grad_on_input_, "relu_grad_on_input is an extension of the fp32 3x3 engine");
@@ -754,60 +747,39 @@ bool ConvGradientOp<float, HIPContext>::RunFloat16Pointwise() {
   CAFFE_ENFORCE(dY.ndim() == 4 && dY.dim32(0) == N && dY.dim32(1) == M && dY.dim32(2) == OH && dY.dim32(3) == OW,
                 "output gradient shape does not match the convolution output");
   hipStream_t s = context_.hip_stream();
-  auto& xb = f16_scratch_[0];
-  auto& dyb = f16_scratch_[1];
-  xb.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
-  dyb.Resize((TIndex)((BlockedHalves(N, M, OH, OW) + 1) / 2));
-  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(X.raw_data(), N, C, H, W, xb.mutable_data<float>(), s), 0);
-  CAFFE_ENFORCE_EQ(ssad_f16_block_activations(dY.raw_data(), N, M, OH, OW, dyb.mutable_data<float>(), s), 0);
-  const float* xs = xb.data<float>();
+  const float* xb = Blocked(X, N, C, H, W, &x_blocked_, s);
+  const float* dyb = Blocked(dY, N, M, OH, OW, &dy_blocked_, s);
+  const float* xs = xb;
   if (st > 1) {                                 // the strided layer's view of its input (odd maps included)
-    auto& sub = f16_scratch_[6];
-    sub.Resize((TIndex)((BlockedHalves(N, C, OH, OW) + 1) / 2));
-    CAFFE_ENFORCE_EQ(ssad_f16_subsample(xb.data<float>(), N, C, H, W, st, sub.mutable_data<float>(), s), 0);
-    xs = sub.data<float>();
+    x_subsampled_.Resize((TIndex)((BlockedHalves(N, C, OH, OW) + 1) / 2));
+    CAFFE_ENFORCE_EQ(ssad_f16_subsample(xb, N, C, H, W, st, x_subsampled_.mutable_data<float>(), s), 0);
+    xs = x_subsampled_.data<float>();
   }
-  auto& dw32 = f16_scratch_[2];
-  auto& db32 = f16_scratch_[3];
-  dw32.Resize((TIndex)filter.size());
-  db32.Resize(M);
+  dfilter_f32_.Resize((TIndex)filter.size());
+  dbias_f32_.Resize(M);
   const size_t wsb = ssad_conv1x1_wgrad_f16_workspace_bytes(N, C, OH, OW, M);
   workspace_.Resize((TIndex)wsb);
-  CAFFE_ENFORCE_EQ(ssad_conv1x1_wgrad_f16(xs, dyb.data<float>(), N, C, OH, OW, M, 0, 1.0f, nullptr,
-                                          dw32.mutable_data<float>(), no_bias_ ? nullptr : db32.mutable_data<float>(),
+  CAFFE_ENFORCE_EQ(ssad_conv1x1_wgrad_f16(xs, dyb, N, C, OH, OW, M, 0, 1.0f, nullptr, dfilter_f32_.mutable_data<float>(),
+                                          no_bias_ ? nullptr : dbias_f32_.mutable_data<float>(),
                                           workspace_.mutable_data<uint8_t>(), wsb, s),
                    0, "float16 pointwise ConvGradient (filter) launch failed");
-  dfilter->ResizeLike(filter);
-  CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(dw32.data<float>(), dfilter->raw_mutable_data(TypeMeta::Make<float16>()),
-                                        filter.size(), s), 0);
-  if (!no_bias_) {
-    auto* dbias = Output(BIAS_OR_INPUT_GRAD);
-    dbias->Resize(M);
-    CAFFE_ENFORCE_EQ(ssad_cast_f32_to_f16(db32.data<float>(), dbias->raw_mutable_data(TypeMeta::Make<float16>()),
-                                          M, s), 0);
-  }
-  if (OutputSize() == 3 || (no_bias_ && OutputSize() == 2)) {
+  EmitFloat16FilterGrads(filter, M);
+  if (auto* dX = DataGradOutput()) {
     CAFFE_ENFORCE(C % 8 == 0, "float16 pointwise ConvGradient: the input width must be a multiple of 8 channels");
-    auto* dX = Output(no_bias_ ? BIAS_OR_INPUT_GRAD : INPUT_GRAD);
-    dX->ResizeLike(X);
-    auto& wf32 = f16_scratch_[4];
-    wf32.Resize((TIndex)filter.size());
-    CAFFE_ENFORCE_EQ(ssad_cast_f16_to_f32(filter.raw_data(), wf32.mutable_data<float>(), filter.size(), s), 0);
+    const float* wf32 = FilterAsF32(filter, &filter_f32_, s);
     packed_filter_.Resize((TIndex)((ssad_pw_f16_filter_halves(M, C) + 1) / 2));
     float* packed = packed_filter_.mutable_data<float>();
-    CAFFE_ENFORCE_EQ(ssad_pw_f16_pack_filter(wf32.data<float>(), M, C, nullptr, packed, s), 0);
-    auto& dxs = f16_scratch_[5];
-    dxs.Resize((TIndex)((BlockedHalves(N, C, OH, OW) + 1) / 2));
-    const ssad_pw_f16 d{dyb.data<float>(), packed, nullptr, nullptr, nullptr, dxs.mutable_data<float>(),
+    CAFFE_ENFORCE_EQ(ssad_pw_f16_pack_filter(wf32, M, C, nullptr, packed, s), 0);
+    out_blocked_.Resize((TIndex)((BlockedHalves(N, C, OH, OW) + 1) / 2));
+    const ssad_pw_f16 d{dyb, packed, nullptr, nullptr, nullptr, out_blocked_.mutable_data<float>(),
                         N, M, C, OH, OW, OH, OW, 1, 0};
     CAFFE_ENFORCE_EQ(ssad_conv1x1_f16(&d, s), 0, "float16 pointwise ConvGradient (data) launch failed");
-    const float* full = dxs.data<float>();
+    const float* full = out_blocked_.data<float>();
     if (st > 1) {
-      auto& up = f16_scratch_[7];
-      up.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
-      CAFFE_ENFORCE_EQ(ssad_f16_elementwise(1, dxs.data<float>(), nullptr, up.mutable_data<float>(), N, C, H, W, st,
-                                            0, s), 0);
-      full = up.data<float>();
+      dx_upsampled_.Resize((TIndex)((BlockedHalves(N, C, H, W) + 1) / 2));
+      CAFFE_ENFORCE_EQ(ssad_f16_elementwise(1, full, nullptr, dx_upsampled_.mutable_data<float>(), N, C, H, W, st, 0,
+                                            s), 0);
+      full = dx_upsampled_.data<float>();
     }
     CAFFE_ENFORCE_EQ(ssad_f16_unblock_activations(full, N, C, H, W, dX->raw_mutable_data(TypeMeta::Make<float16>()),
                                                   s), 0);

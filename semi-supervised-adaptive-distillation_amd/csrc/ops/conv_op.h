@@ -31,7 +31,7 @@
 //   Conv          fuse_sigmoid=1          Y = 1 / (1 + exp(-conv))  (Conv + Sigmoid; the 3x3 fp32 engines)
 //   ConvGradient  relu_grad_on_input=1    dX masked by X > 0 (= ReluGradient of
 //                                         the in-place Relu that produced X)
-//   both          hip_algo="direct"|"winograd"   pin the algorithm (default: by width)
+//   both          hip_algo                which 3x3 engine: the rule and its strings are in ops/conv3x3_engine.h
 //   both          hip_algo="grouped"      opt-in: a grouped 3x3 / pad 1 / stride 1|2 layer with 4, 8, 16, 32 or 64
 //                                         channels per group (ResNeXt) on kernels/grouped_conv3x3{,_grad}.hip instead
 //                                         of the default engine; any other geometry fails by name (no fall-back)
@@ -146,7 +146,45 @@ ConvGeometry ParseConvGeometry(const OperatorBase& op);
 ConvGeometry ParseConvGeometry(const OperatorDef& def);
 bool IsSubnetGeometry(const ConvGeometry& g);   // 3x3 / s1 / p1 / d1 / g1 / NCHW
 bool IsDefaultEngineGeometry(const ConvGeometry& g);   // any 2-D NCHW geometry (group >= 1)
-bool UseWinograd(const string& algo, int out_channels);
+
+// One 3x3 / stride 1 / pad 1 fp32 problem of the operator surface.  A Conv is a ConvGroup of one problem, a
+// ConvGradient a ConvGradientGroup of one problem and one filter: all four operators run on a Conv3x3Runner.
+struct Conv3x3Problem {
+  const Tensor<HIPContext>* x = nullptr;
+  const Tensor<HIPContext>* w = nullptr;
+  const Tensor<HIPContext>* b = nullptr;     // forward: bias (or null); gradient: dY
+  Tensor<HIPContext>* y = nullptr;           // forward: Y; gradient: dX (or null)
+  int N = 0, C = 0, H = 0, W = 0, M = 0;
+  Conv3x3Problem() {}
+  Conv3x3Problem(const Tensor<HIPContext>& x_, const Tensor<HIPContext>& w_, const Tensor<HIPContext>* b_,
+                 Tensor<HIPContext>* y_)
+      : x(&x_), w(&w_), b(b_), y(y_), N(x_.dim32(0)), C(x_.dim32(1)), H(x_.dim32(2)), W(x_.dim32(3)), M(w_.dim32(0)) {}
+};
+
+// The launch path of the 3x3 engines: the packed filters (ops/filter_pack_cache.h), the split-operand engine's and the
+// filter gradient's workspaces, the engine of each launch by the rule of ops/conv3x3_engine.h.  `what` is the text of
+// a failed launch.
+class Conv3x3Runner {
+ public:
+  // One launcher call per class of equal (M, C), classes in order of first appearance, per SSAD_MAX_CONV_PROBLEMS
+  // problems; after one pack launch per layout for the filters written since.  dgrad = false: y = conv(x, w) + b under
+  // `flags`.  dgrad = true: the data gradient, y (dX, C channels) from b (dY, M channels) on the flipped / transposed
+  // pack, masked by x > 0 when flags has SSAD_CONV_MASK_AUX.
+  void Forward(const vector<Conv3x3Problem>& probs, const string& algo, int flags, bool dgrad, const char* what,
+               hipStream_t s);
+  // dW (and db unless null) of one [M][C][3][3] filter, reduced over the problems `mine` that read it (SSAD_MAX_LEVELS
+  // a launch, the later launches accumulating); overwrite, beta = 0 (conv_op_cudnn.cc:1037).
+  void FilterGradient(const vector<Conv3x3Problem>& probs, const vector<int>& mine, float* dW, float* db, int M, int C,
+                      const string& algo, const char* what, hipStream_t s);
+  // want, flush, count, packed for one filter (the route of hip_algo = "grouped")
+  const float* Pack(const Tensor<HIPContext>& filter, FilterPackCache::Kind kind, hipStream_t s);
+
+ private:
+  void FlushPacks(hipStream_t s);
+  FilterPackCache cache_;
+  SplitEngine split_;
+  Tensor<HIPContext> wgrad_workspace_;     // grows to the largest launch seen
+};
 
 template <typename T, class Context>
 class ConvOp final : public Operator<Context> {
@@ -172,10 +210,10 @@ class ConvOp final : public Operator<Context> {
   int fuse_sigmoid_;                    // Y = sigmoid(conv) (set by the net lowering: Conv -> Sigmoid; 3x3 fp32 path only)
   string algo_;
   Tensor<Context> packed_filter_;
-  FilterPackCache pack_cache_;
-  SplitEngine split_;
+  Conv3x3Runner runner_;
   Tensor<Context> col_buffer_;
-  Tensor<Context> f16_scratch_[4];
+  // float16 blobs: the filter and the bias as fp32, X and Y channel-blocked (Y as NCHW fp32 where M % 8)
+  Tensor<Context> filter_f32_, bias_f32_, x_blocked_, out_blocked_;
   bool RunFloat16Pointwise();
 };
 
@@ -205,12 +243,20 @@ class ConvGradientOp final : public Operator<Context> {
   bool RunDefaultEngine();
   bool RunGrouped();
   bool RunFloat16();
+  // the dX output, resized like X -- or null where the definition has none (conv_gradient_op.cc:35-77)
+  Tensor<Context>* DataGradOutput();
+  // dbias = the channel sums of dY [N][M][P] (nothing under no_bias)
+  void EmitBiasGrad(const Tensor<Context>& dY, int N, int M, int P);
+  // float16 blobs: dfilter and dbias from their fp32 sums
+  void EmitFloat16FilterGrads(const Tensor<Context>& filter, int M);
   Tensor<Context> packed_filter_;
-  FilterPackCache pack_cache_;
-  SplitEngine split_;
+  Conv3x3Runner runner_;
   Tensor<Context> workspace_;
   Tensor<Context> col_buffer_;
-  Tensor<Context> f16_scratch_[8];
+  // float16 blobs: X and dY channel-blocked, the filter and bias gradients' fp32 sums, the filter as fp32, dX
+  // channel-blocked (as NCHW fp32 where C % 8); the strided pointwise layer's subsampled X and upsampled dX
+  Tensor<Context> x_blocked_, dy_blocked_, dfilter_f32_, dbias_f32_, filter_f32_, out_blocked_, x_subsampled_,
+      dx_upsampled_;
   bool RunFloat16Pointwise();
 };
 

@@ -12,6 +12,7 @@
 #include <map>
 
 #include "c2/operator.h"
+#include "ops/conv3x3_engine.h"
 #include "ssad_kernels.h"
 
 namespace caffe2 {
@@ -21,6 +22,14 @@ class FilterPackCache {
   enum Kind { WINO_FWD = 0, WINO_DGRAD = 1, DIRECT_FWD = 2, DIRECT_DGRAD = 3, WINO24_FWD = 4, WINO24_DGRAD = 5,
               SPLIT_FWD = 6, SPLIT_DGRAD = 7,       // 6 / 7: the split-operand engine's packs (conv3x3_split.hip)
               GROUPED_FWD = 8, GROUPED_DGRAD = 9 }; // hip_algo = "grouped": filter [C][C/group][3][3], group = M / C
+  // What the order of the enum encodes: (forward, data gradient) pairs, one per engine, the grouped pair last.
+  static bool IsDgrad(Kind kind) { return (kind & 1) != 0; }
+  static bool IsGrouped(Kind kind) { return kind >= GROUPED_FWD; }
+  static Conv3x3Engine EngineOf(Kind kind) {     // of a kind that is not grouped
+    constexpr Conv3x3Engine by_pair[] = {Conv3x3Engine::WINO, Conv3x3Engine::DIRECT, Conv3x3Engine::WINO24,
+                                         Conv3x3Engine::SPLIT};
+    return by_pair[kind >> 1];
+  }
 
   // Queue `filter` ([M][C][3][3], fp32) for layout `kind`; Flush() issues the packs that are stale
   // (one multi-filter launch for the Winograd layouts) on `stream`; Packed() is valid after it.
@@ -40,19 +49,23 @@ class FilterPackCache {
     e.C = C;
     e.version = filter.version();
     e.uid = filter.uid();
-    const bool dgrad = kind == WINO_DGRAD || kind == DIRECT_DGRAD || kind == WINO24_DGRAD || kind == SPLIT_DGRAD;
-    const bool wino = kind == WINO_FWD || kind == WINO_DGRAD;
-    const int po = dgrad ? C : M, pi = dgrad ? M : C;       // the pack's (outputs, inputs)
-    const bool grouped = kind == GROUPED_FWD || kind == GROUPED_DGRAD;
-    const long long gfloats = !grouped || C < 1 || M % C ? -1
-                              : kind == GROUPED_FWD ? ssad_grouped_conv3x3_filter_floats(M, M / C)
-                                                    : ssad_grouped_conv3x3_dgrad_filter_floats(M, M / C);
-    CAFFE_ENFORCE(!grouped || gfloats > 0, "grouped 3x3 engine: ", M, " channels with ", C,
-                  " per group (4, 8, 16, 32 or 64 per group)");
-    e.packed.Resize((TIndex)(grouped ? (size_t)gfloats
-                             : (kind == SPLIT_FWD || kind == SPLIT_DGRAD) ? ssad_conv_split_filter_floats(po, pi)
-                             : (kind == WINO24_FWD || kind == WINO24_DGRAD) ? ssad_conv_wino24_filter_floats(po, pi)
-                             : wino ? ssad_conv_wino_filter_floats(po, pi) : ssad_conv_packed_filter_floats(po, pi)));
+    size_t floats;
+    if (IsGrouped(kind)) {
+      const long long g = C < 1 || M % C ? -1
+                          : IsDgrad(kind) ? ssad_grouped_conv3x3_dgrad_filter_floats(M, M / C)
+                                          : ssad_grouped_conv3x3_filter_floats(M, M / C);
+      CAFFE_ENFORCE(g > 0, "grouped 3x3 engine: ", M, " channels with ", C, " per group (4, 8, 16, 32 or 64 per group)");
+      floats = (size_t)g;
+    } else {
+      const int po = IsDgrad(kind) ? C : M, pi = IsDgrad(kind) ? M : C;       // the pack's (outputs, inputs)
+      switch (EngineOf(kind)) {
+        case Conv3x3Engine::SPLIT: floats = ssad_conv_split_filter_floats(po, pi); break;
+        case Conv3x3Engine::WINO24: floats = ssad_conv_wino24_filter_floats(po, pi); break;
+        case Conv3x3Engine::WINO: floats = ssad_conv_wino_filter_floats(po, pi); break;
+        default: floats = ssad_conv_packed_filter_floats(po, pi); break;
+      }
+    }
+    e.packed.Resize((TIndex)floats);
     e.packed.mutable_data<float>();
     e.queued = true;
     e.src = filter.data<float>();
@@ -123,8 +136,17 @@ class FilterPackCache {
   long long packs_issued_ = 0;
 };
 
-// hip_algo = "split" (assigned by the net lowering): the split-operand engine for >= 128-wide problems.  Its
-// workspace (the split copy of the launch's inputs) belongs to the operator and grows to the largest launch seen.
+// the layout `engine` reads, forward or data gradient: the inverse of IsDgrad / EngineOf
+inline FilterPackCache::Kind PackKindOf(Conv3x3Engine engine, bool dgrad) {
+  const int fwd = engine == Conv3x3Engine::SPLIT    ? FilterPackCache::SPLIT_FWD
+                  : engine == Conv3x3Engine::WINO24 ? FilterPackCache::WINO24_FWD
+                  : engine == Conv3x3Engine::WINO   ? FilterPackCache::WINO_FWD
+                                                    : FilterPackCache::DIRECT_FWD;
+  return (FilterPackCache::Kind)(fwd + (dgrad ? 1 : 0));
+}
+
+// The split-operand engine (hip_algo = "split", assigned by the net lowering; ops/conv3x3_engine.h says for which
+// problems).  Its workspace (the split copy of the launch's inputs) belongs to the operator and grows to the largest launch seen.
 class SplitEngine {
  public:
   int Run(const ssad_conv_level* lv, int n, const float* packed, const float* bias, int M, int C, int flags,
