@@ -697,15 +697,23 @@ static int wgrad_plan(const ssad_conv_level* lv, int n_levels, int Cout, int Cin
   return 0;
 }
 
+// The workspace of a planned filter gradient: the partial-sum slabs, sized for either engine so the choice can change
+// between calls, then the bias gradient's partial sums (at `slab`, need - slab bytes).
+struct WgWorkspace {
+  size_t slab, need;
+};
+static WgWorkspace wgrad_workspace(const WgArgs& a, const ssad_conv_level* lv, int n_levels, int Cout, int Cin) {
+  size_t slab = sizeof(float) * (size_t)a.splits * a.mblocks * WG_MT * a.cblocks * WG_CT * 9 * 1024;
+  const size_t wino = ssad_wino_wgrad_workspace_bytes(lv, n_levels, Cout, Cin);
+  if (wino > slab) slab = wino;
+  return WgWorkspace{slab, slab + sizeof(double) * (size_t)Cout * kBiasParts};
+}
+
 size_t ssad_conv3x3_wgrad_workspace_bytes(const ssad_conv_level* levels_host, int n_levels,
                                           int Cout, int Cin) {
   WgArgs a;
   if (wgrad_plan(levels_host, n_levels, Cout, Cin, &a)) return 0;
-  size_t slab = sizeof(float) * (size_t)a.splits * a.mblocks * WG_MT * a.cblocks * WG_CT * 9 * 1024;
-  // sized for either engine, so the choice can change between calls
-  const size_t wino = ssad_wino_wgrad_workspace_bytes(levels_host, n_levels, Cout, Cin);
-  if (wino > slab) slab = wino;
-  return slab + sizeof(double) * (size_t)Cout * kBiasParts;
+  return wgrad_workspace(a, levels_host, n_levels, Cout, Cin).need;
 }
 
 int ssad_conv3x3_wgrad(const ssad_conv_level* levels_host, int n_levels, float* dW, float* db,
@@ -718,11 +726,9 @@ int ssad_conv3x3_wgrad(const ssad_conv_level* levels_host, int n_levels, float* 
     if (!levels_host[l].aux && levels_host[l].N * levels_host[l].H * levels_host[l].W > 0)
       return SSAD_E_BADARG;
   const int mtp = a.mblocks * WG_MT, ctp = a.cblocks * WG_CT;
-  size_t slab_bytes = sizeof(float) * (size_t)a.splits * mtp * ctp * 9 * 1024;
-  const size_t wino_bytes = ssad_wino_wgrad_workspace_bytes(levels_host, n_levels, Cout, Cin);
-  if (wino_bytes > slab_bytes) slab_bytes = wino_bytes;
-  const size_t need = slab_bytes + sizeof(double) * (size_t)Cout * kBiasParts;
-  if (!workspace || workspace_bytes < need) return SSAD_E_WORKSPACE;
+  const WgWorkspace ws = wgrad_workspace(a, levels_host, n_levels, Cout, Cin);
+  const size_t slab_bytes = ws.slab;
+  if (!workspace || workspace_bytes < ws.need) return SSAD_E_WORKSPACE;
   a.slabs = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
   if (ssad_wino_wgrad_eligible(Cout, Cin)) {

@@ -611,29 +611,22 @@ size_t ssad_conv_split_filter_floats(int M, int K) {
 }
 
 int ssad_conv_split_pack_filters(const ssad_pack_entry* entries_host, int n_entries, ssad_stream_t stream) {
-  if (n_entries < 0 || (n_entries > 0 && !entries_host)) return SSAD_E_BADARG;
-  for (int base = 0; base < n_entries; base += SSAD_MAX_PACK_ENTRIES) {
-    const int cnt = n_entries - base < SSAD_MAX_PACK_ENTRIES ? n_entries - base : SSAD_MAX_PACK_ENTRIES;
-    FPackTable t;
+  return ssad_for_pack_chunks<FPackTable>(entries_host, n_entries, /*need_dst=*/true, [&](const FPackTable& t, int cnt) {
     long long smax = 0;
     bool any_dgrad = false;
     for (int i = 0; i < cnt; ++i) {
-      const ssad_pack_entry& e = entries_host[base + i];
-      if (e.Cout <= 0 || e.Cin <= 0 || !e.w || (!e.packed_fwd && !e.packed_dgrad)) return SSAD_E_BADARG;
-      t.e[i] = e;
+      const ssad_pack_entry& e = t.e[i];
       const long long sf = 9LL * ((e.Cin + 7) >> 3) * e.Cout, sd = 9LL * ((e.Cout + 7) >> 3) * e.Cin;
       smax = sf > smax ? sf : smax;
       if (e.packed_dgrad) { smax = sd > smax ? sd : smax; any_dgrad = true; }
     }
-    for (int i = cnt; i < SSAD_MAX_PACK_ENTRIES; ++i) t.e[i] = ssad_pack_entry{};
     hipLaunchKernelGGL(split_filter_zero_kernel, dim3((unsigned)cnt), dim3(64), 0, (hipStream_t)stream, t);
     hipLaunchKernelGGL(split_filter_amax_kernel, dim3(64u, (unsigned)cnt), dim3(kThreads), 0, (hipStream_t)stream, t);
     long long bx = (smax + kThreads - 1) / kThreads;
     if (bx > 512) bx = 512;
     hipLaunchKernelGGL(split_filter_pack_kernel, dim3((unsigned)bx, (unsigned)cnt, any_dgrad ? 2u : 1u), dim3(kThreads), 0,
                        (hipStream_t)stream, t);
-  }
-  return (int)hipGetLastError();
+  });
 }
 
 size_t ssad_conv3x3_split_workspace_bytes(const ssad_conv_level* lv, int n_levels, int Cin) {

@@ -37,26 +37,26 @@
 
 #include "conv_internal.h"
 #include "ssad_kernels.h"
+#include "wino_launch.h"
 
 namespace {
+
+// shared with the F(2x4) engine and the launch planner (wino_launch.h)
+using ssad_wino::PR; using ssad_wino::PC; using ssad_wino::SP; using ssad_wino::BM; using ssad_wino::KC;
+using ssad_wino::ZNT; using ssad_wino::kBlock; using ssad_wino::kNoSub; using ssad_wino::kOOBOff;
+using ssad_wino::WLevel; using ssad_wino::WTile;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef WINO_KC
-#define WINO_KC 16
-#endif
-constexpr int KC = WINO_KC;      // input channels per chunk (multiple of 8)
-constexpr int KS = KC / 4;       // MFMA k-steps (4 channels each) per chunk
+constexpr int KS = KC / 4;       // MFMA k-steps (4 channels each) per chunk of KC input channels
 constexpr int STEPS = KS * 4;    // A-stream float4 per lane per chunk
-constexpr int PR = 8, PC = 16;   // output patch rows / cols (4 x 8 tiles of 2x2)
+// (the output patch, PR x PC = 8 x 16, is 4 x 8 tiles of 2x2)
 constexpr int RP = 20;           // raw LDS row pitch (18 used)
 constexpr int RS = (PR + 2) * RP;        // raw floats per channel
 constexpr int RAW = KC * RS;             // raw floats per buffer
 constexpr int VP = 32;                   // V channel pitch: 32 tiles stored as [tile&15][tile>>4]
 constexpr int VBUF = 16 * KC * VP;       // transformed floats per buffer
-constexpr int kBlock = 512;
-constexpr int BM = 128;                  // output channels per workgroup
 
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
@@ -133,21 +133,6 @@ __global__ void wino_pack_multi_kernel(const PackTable t) {
 // ---------------------------------------------------------------------------
 // Convolution
 // ---------------------------------------------------------------------------
-struct WLevel {
-  const float* x;
-  float* y;
-  const float* aux;
-  const float* packed;
-  const float* bias;
-  int N, H, W;
-  int tiles_x, tiles_y;
-  int block_start;
-  // persistent variant: 8 x 8-pixel sub-patches, two per work item
-  int sub_x, sub_y;       // sub-patches per row / column of one image
-  int pair_start;         // first work item of this level
-};
-
-
 struct WArgs {
   WLevel lv[SSAD_MAX_CONV_PROBLEMS];
   int n_levels;
@@ -165,7 +150,6 @@ struct WArgs {
 };
 
 constexpr int NRAW = 3;
-constexpr unsigned kOOBOff = 0x80000000u;
 
 // WINO_ABLATE (debug builds only, results are wrong): 1 = no raw-patch DMA in the loop, 2 = no input transform,
 // 4 = filter operand ring not refilled, 8 = B operands not re-read, 16 = no epilogue, 32 = no per-chunk barrier
@@ -187,14 +171,8 @@ __device__ unsigned long long g_wv[8][64][2];     // per wave of the stamped wor
 #define DBGW(it, k)
 #endif
 
-// One work item of the persistent kernel: two 8 x 8-pixel sub-patches of one level (4 x 4 tiles each = the two
-// tile groups of the MFMAs), each with its own image and origin; y0 = kNoSub marks an absent partner.
-struct WTile {
-  int l, mb;
-  int n[2], y0[2], x0[2];
-};
-constexpr int SP = 8;                     // sub-patch edge (output pixels)
-constexpr int kNoSub = 1 << 24;
+// One work item of the persistent kernel (WTile): two 8 x 8-pixel sub-patches of one level, 4 x 4 tiles each = the two
+// tile groups of the MFMAs.
 
 // ---------------------------------------------------------------------------
 // Variant Z: persistent, 8 symmetric waves, LDS-DMA staging, everything
@@ -229,7 +207,6 @@ constexpr int ZCP = (PR + 2) * ZP;        // 400 floats per channel pair
 constexpr int ZRAW = (KC / 2) * ZCP;      // 3200 floats = 50 wave-loads
 constexpr int ZL = 7;                     // wave-loads per wave per chunk (8 x 7 = 56 >= 50)
 constexpr int ZRAWP = 8 * ZL * 64;        // padded raw buffer (dummy loads land in the pad)
-constexpr int ZNT = 256;                  // tiles per workgroup in the LDS list
 constexpr int AD = 8;                     // filter operand ring depth (steps)
 static_assert(ZRAW <= ZRAWP && STEPS == 16 && AD == 8, "variant Z is written for KC = 16");
 
@@ -923,25 +900,16 @@ __global__ __launch_bounds__(kBlock, 1) void wino_conv_z_kernel(const WArgs args
 
 }  // namespace
 
-// Scratch of the split tail: one 64 KB slot per workgroup of the grid + the arrival counters, per (device, stream)
-// -- launches on different streams run concurrently and must not share it; launches on one stream are ordered.
-// Allocated on a stream's first split launch (during warm-up), never freed, never grown (the size depends on the
-// device's CU count only); the counters are zeroed once and left zero by every launch.
+// ssad_conv_wino_split_tail's setting (SSAD_WINO_SPLIT_TAIL=0: rounds 1-4's behaviour, no split anywhere)
 static std::atomic<int>& split_tail_setting() {
   static std::atomic<int> on([] { const char* e = getenv("SSAD_WINO_SPLIT_TAIL"); return (e && *e) ? atoi(e) : 1; }());
   return on;
 }
 
-// Units per tail item (1 = no split): the largest power of two p with  p <= 8,  tail * p <= grid,  p | chunks  and
-// chunks / p >= 2.  *full = items of the whole rounds, *tail = items of the partial round.
-static int split_plan(long long total, int chunks, int cus, long long* full, long long* tail) {
-  *full = (total / cus) * cus;
-  *tail = total - *full;
-  int p = 1;
-  while (*tail > 0 && p * 2 <= 8 && *tail * (p * 2) <= cus && chunks % (p * 2) == 0 && chunks / (p * 2) >= 2) p *= 2;
-  return p;
-}
-
+// Scratch of the split tail: one 64 KB slot per workgroup of the grid + the arrival counters, per (device, stream)
+// -- launches on different streams run concurrently and must not share it; launches on one stream are ordered.
+// Allocated on a stream's first split launch (during warm-up), never freed, never grown (the size depends on the
+// device's CU count only); the counters are zeroed once and left zero by every launch.
 static int split_scratch(hipStream_t stream, int units, void** ws, unsigned** tickets) {
   static std::mutex mu;
   static std::map<std::pair<int, hipStream_t>, void*> table;
@@ -959,6 +927,26 @@ static int split_scratch(hipStream_t stream, int units, void** ws, unsigned** ti
   }
   *ws = base;
   *tickets = (unsigned*)((char*)base + ws_bytes);
+  return 0;
+}
+
+// The passes of one call, by the planner and the split-tail decision of wino_launch.h: `launch(pass, tail, use_pairs)`
+// per staging geometry present.  The launcher and both launch counts walk a level table through this and nothing
+// else.  Stops at the first pass that is refused and returns its code.
+template <class Launch>
+static int for_each_pass(const ssad_conv_level* lv, int n_levels, const float* packed, const float* bias, int Cout,
+                         int Cin, int flags, ssad_wino::WLevel* out, Launch launch) {
+  const int cus = ssad_cu_count();
+  const bool half = Cout <= 64;
+  // pass 0: the levels staged as 8 x 16 patches; pass 1: those staged as sub-patch pairs
+  for (int pass = 0; pass < 2; ++pass) {
+    const ssad_wino::Pass p = ssad_wino::plan_pass(lv, n_levels, packed, bias, pass == 1, cdiv(Cout, BM), cus, out);
+    if (p.rc) return p.rc;
+    if (p.nl == 0) continue;
+    const int rc = launch(p, ssad_wino::plan_split_tail(p.total, cdiv(Cin, KC), cus, split_tail_setting().load(), flags,
+                                                        half), pass == 1);
+    if (rc) return rc;
+  }
   return 0;
 }
 
@@ -980,80 +968,45 @@ int ssad_conv_wino_pack_filter(const float* w, int Cout, int Cin, float* packed_
 }
 
 int ssad_conv_wino_pack_filters(const ssad_pack_entry* entries_host, int n_entries, ssad_stream_t stream) {
-  if (n_entries < 0 || (n_entries > 0 && !entries_host)) return SSAD_E_BADARG;
-  for (int base = 0; base < n_entries; base += SSAD_MAX_PACK_ENTRIES) {
-    const int cnt = n_entries - base < SSAD_MAX_PACK_ENTRIES ? n_entries - base : SSAD_MAX_PACK_ENTRIES;
-    PackTable t;
+  // an entry with neither destination is accepted; a chunk with nothing to write launches nothing
+  return ssad_for_pack_chunks<PackTable>(entries_host, n_entries, /*need_dst=*/false, [&](const PackTable& t, int cnt) {
     size_t nmax = 0;
     for (int i = 0; i < cnt; ++i) {
-      const ssad_pack_entry& e = entries_host[base + i];
-      if (e.Cout <= 0 || e.Cin <= 0 || !e.w) return SSAD_E_BADARG;
-      t.e[i] = e;
+      const ssad_pack_entry& e = t.e[i];
       const size_t nf = e.packed_fwd ? ssad_conv_wino_filter_floats(e.Cout, e.Cin) : 0;
       const size_t nd = e.packed_dgrad ? ssad_conv_wino_filter_floats(e.Cin, e.Cout) : 0;
       nmax = nf > nmax ? nf : nmax;
       nmax = nd > nmax ? nd : nmax;
     }
-    for (int i = cnt; i < SSAD_MAX_PACK_ENTRIES; ++i) t.e[i] = ssad_pack_entry{};
-    if (nmax == 0) continue;
+    if (nmax == 0) return;
     size_t bx = (nmax + 255) / 256;
     if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(wino_pack_multi_kernel, dim3((unsigned)bx, (unsigned)cnt), dim3(256), 0,
                        (hipStream_t)stream, t);
-  }
-  return (int)hipGetLastError();
-}
-
-// Geometry of the persistent kernel per level: 8 x 16 patches where they tile the map exactly or the 8 x 8
-// sub-patches would not save pixels (a patch stages 18 columns where two sub-patches stage 20: ~4 % faster per
-// computed pixel), sub-patch pairs elsewhere.  SSAD_WINO_PAIRS=0 / 1 forces one geometry for every level.
-static bool level_wants_pairs(int N, int H, int W) {
-  static const int geom = [] { const char* e = getenv("SSAD_WINO_PAIRS"); return (e && *e) ? atoi(e) : -1; }();
-  if (geom >= 0) return geom != 0;
-  const long long by_patch = (long long)cdiv(W, PC) * cdiv(H, PR) * 128;
-  const long long by_sub = (long long)cdiv(W, SP) * cdiv(H, SP) * 64;
-  (void)N;
-  return by_sub * 100 <= by_patch * 96;
+  });
 }
 
 // number of kernel launches one call makes (1, or 2 when both geometries occur); tools/pmc_by_class.py
 // attributes counters to timing classes by launch order
 int ssad_conv3x3_forward_wino_launches(const ssad_conv_level* lv, int n_levels) {
   if (!lv || n_levels < 1) return 0;
-  int with_pairs = 0, with_patches = 0;
-  for (int l = 0; l < n_levels; ++l) {
-    if ((long long)lv[l].N * lv[l].H * lv[l].W == 0) continue;
-    if (level_wants_pairs(lv[l].N, lv[l].H, lv[l].W)) ++with_pairs; else ++with_patches;
-  }
-  return (with_pairs > 0) + (with_patches > 0);
+  int launches = 0;
+  // one per staging geometry present (any channel counts that never split: 36 run the half-block kernels)
+  for_each_pass(lv, n_levels, nullptr, nullptr, 36, 36, 0, nullptr,
+                [&](const ssad_wino::Pass&, const ssad_wino::Tail&, bool) { ++launches; return 0; });
+  return launches;
 }
 
-// ... and with the split tails of this (Cout, Cin): + 1 per geometry whose partial round is split
+// ... and with the split tails of this (Cout, Cin): + 1 per geometry whose partial round is split off behind full
+// rounds.  (Assumes the launcher gets its split scratch, see plan_split_tail.)
 int ssad_conv3x3_forward_wino_launches_for(const ssad_conv_level* lv, int n_levels, int Cout, int Cin, int flags) {
   if (!lv || n_levels < 1 || Cout <= 0 || Cin <= 0) return 0;
-  constexpr int nhalf = 1;
-  const bool half = nhalf && Cout <= 64;
-  const int cus = ssad_cu_count();
   int launches = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    long long blocks = 0, pairs = 0;
-    int nl = 0;
-    for (int l = 0; l < n_levels; ++l) {
-      if ((long long)lv[l].N * lv[l].H * lv[l].W == 0) continue;
-      if (level_wants_pairs(lv[l].N, lv[l].H, lv[l].W) != (pass == 1)) continue;
-      ++nl;
-      blocks += (long long)lv[l].N * cdiv(lv[l].W, PC) * cdiv(lv[l].H, PR);
-      pairs += ((long long)lv[l].N * cdiv(lv[l].W, SP) * cdiv(lv[l].H, SP) + 1) / 2;
-    }
-    if (!nl) continue;
-    const long long total = (pass == 1 ? pairs : blocks) * cdiv(Cout, BM);
-    long long full = 0, tail = 0;
-    int mode = split_tail_setting().load();
-    if (mode && (flags & SSAD_CONV_SPLIT_TAIL)) mode = 2;
-    int p = (mode && !half && total <= (long long)cus * ZNT) ? split_plan(total, cdiv(Cin, KC), cus, &full, &tail) : 1;
-    if (mode < 2 && full > 0) p = 1;
-    launches += p >= 2 ? (full > 0) + 1 : 1;
-  }
+  for_each_pass(lv, n_levels, nullptr, nullptr, Cout, Cin, flags, nullptr,
+                [&](const ssad_wino::Pass&, const ssad_wino::Tail& t, bool) {
+                  launches += t.parts ? (t.full > 0) + 1 : 1;
+                  return 0;
+                });
   return launches;
 }
 
@@ -1066,104 +1019,42 @@ int ssad_conv_wino_split_tail(int on) {
 int ssad_conv3x3_forward_wino(const ssad_conv_level* lv, int n_levels, const float* packed,
                               const float* bias, int Cout, int Cin, int flags,
                               ssad_stream_t stream) {
-  if (n_levels < 1 || n_levels > SSAD_MAX_CONV_PROBLEMS || Cout <= 0 || Cin <= 0)
-    return SSAD_E_BADARG;
-  for (int l = 0; l < n_levels; ++l) {
-    if (!(lv[l].packed ? lv[l].packed : packed)) return SSAD_E_BADARG;
-    if (lv[l].N < 0 || lv[l].H < 0 || lv[l].W < 0) return SSAD_E_BADARG;
-    if ((long long)lv[l].N * lv[l].H * lv[l].W * (Cin > Cout ? Cin : Cout) >= (1LL << 29)) return SSAD_E_BADARG;
-    if ((flags & SSAD_CONV_MASK_AUX) && !lv[l].aux) return SSAD_E_BADARG;
-  }
-  // pass 0: the levels staged as 8 x 16 patches; pass 1: those staged as sub-patch pairs (persistent kernel
-  // only)
-  for (int pass = 0; pass < 2; ++pass) {
-    const bool use_pairs = pass == 1;
-    WArgs a;
-    a.M = Cout; a.K = Cin; a.chunks = cdiv(Cin, KC); a.flags = flags;
-    a.mblocks = cdiv(Cout, BM);
-    int nl = 0;
-    long long blocks = 0, pairs = 0;
-    for (int l = 0; l < n_levels; ++l) {
-      if ((long long)lv[l].N * lv[l].H * lv[l].W == 0) continue;
-      if (level_wants_pairs(lv[l].N, lv[l].H, lv[l].W) != use_pairs) continue;
-      WLevel& L = a.lv[nl++];
-      L.x = lv[l].x; L.y = lv[l].y; L.aux = lv[l].aux;
-      L.packed = lv[l].packed ? lv[l].packed : packed;
-      L.bias = lv[l].packed ? lv[l].bias : bias;
-      L.N = lv[l].N; L.H = lv[l].H; L.W = lv[l].W;
-      L.tiles_x = cdiv(L.W, PC); L.tiles_y = cdiv(L.H, PR);
-      L.block_start = (int)blocks;
-      blocks += (long long)L.N * L.tiles_x * L.tiles_y;
-      L.sub_x = cdiv(L.W, SP); L.sub_y = cdiv(L.H, SP);
-      L.pair_start = (int)pairs;
-      pairs += ((long long)L.N * L.sub_x * L.sub_y + 1) / 2;
-      if (blocks >= (1LL << 31)) return SSAD_E_BADARG;
+  if (const int rc = ssad_wino::check_levels(lv, n_levels, packed, Cout, Cin, flags)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool half = Cout <= 64;        // NHALF
+  WArgs a;
+  a.M = Cout; a.K = Cin; a.chunks = cdiv(Cin, KC); a.flags = flags;   // any Cin: channels past it read as zero
+  a.mblocks = cdiv(Cout, BM);
+  // tiles per XCD run: 8 (1 = round 2's round-robin order: +4 %, profiles/r03_pmc_classes_roundrobin.md)
+  a.xcd_group = 8;
+  return for_each_pass(lv, n_levels, packed, bias, Cout, Cin, flags, a.lv,
+                       [&](const ssad_wino::Pass& p, ssad_wino::Tail t, bool use_pairs) {
+    a.n_levels = p.nl;
+    a.patches = (int)(use_pairs ? p.pairs : p.blocks);
+    void* ws = nullptr;
+    unsigned* tk = nullptr;
+    // no scratch for the units: the unsplit launch
+    if (t.parts && split_scratch(st, ssad_cu_count(), &ws, &tk) != 0) t = ssad_wino::Tail{0, p.total, 0};
+    a.items = (int)t.full;
+    a.full_items = t.parts ? (int)t.full : 0;
+    a.split_parts = t.parts;
+    a.split_ws = (float*)ws;
+    a.split_tickets = tk;
+    // behind a split tail the main launch walks whole rounds of one workgroup per CU
+    const dim3 g3((unsigned)(t.parts ? ssad_cu_count() : p.grid)), b3(kBlock);
+    if (a.items > 0) {
+      if (use_pairs && half) hipLaunchKernelGGL((wino_conv_z_kernel<true, true>), g3, b3, 0, st, a);
+      else if (use_pairs) hipLaunchKernelGGL((wino_conv_z_kernel<true, false>), g3, b3, 0, st, a);
+      else if (half) hipLaunchKernelGGL((wino_conv_z_kernel<false, true>), g3, b3, 0, st, a);
+      else hipLaunchKernelGGL((wino_conv_z_kernel<false, false>), g3, b3, 0, st, a);
     }
-    if (nl == 0) continue;
-    a.n_levels = nl;
-    for (int l = nl; l < SSAD_MAX_CONV_PROBLEMS; ++l) a.lv[l] = WLevel{};
-    {   // any Cin: channels past Cin read as zero (buffer range check, zero-padded filter)
-      const int cus2 = ssad_cu_count();
-      a.patches = (int)(use_pairs ? pairs : blocks);
-      const long long total = (long long)a.patches * a.mblocks;
-      if (total >= (1LL << 31)) return SSAD_E_BADARG;
-      long long grid = total < cus2 ? total : cus2;
-      if (grid * ZNT < total) grid = (total + ZNT - 1) / ZNT;
-      // tiles per XCD run: 8 (1 = round 2's round-robin order: +4 %, profiles/r03_pmc_classes_roundrobin.md)
-      constexpr int xg = 8;
-      constexpr int nhalf = 1;
-      a.xcd_group = xg;
-      const bool half = nhalf && Cout <= 64;
-      // Split tail (round 5, the kernel's header): the items of the last, partial round are cut along the
-      // reduction into p units each and run as a second launch behind the full rounds.  Taken when the partial
-      // round is at most half full (p >= 2); p is a power of two that divides `chunks`, <= 8 and <= chunks / 2,
-      // so that a unit is at least two chunks (its fixed costs: prologue, epilogue, the partial round trip).
-      // SSAD_WINO_SPLIT_TAIL=0: rounds 1-4's behaviour.
-      int split_on = split_tail_setting().load();
-      if (split_on && (flags & SSAD_CONV_SPLIT_TAIL)) split_on = 2;
-      a.items = (int)total;
-      a.full_items = a.split_parts = 0;
-      a.split_ws = nullptr;
-      a.split_tickets = nullptr;
-      long long tail = 0;
-      int parts = 0;
-      if (split_on && !half && grid == (total < cus2 ? total : cus2)) {
-        long long full = 0;
-        const int p = split_plan(total, a.chunks, cus2, &full, &tail);
-        void* ws = nullptr;
-        unsigned* tk = nullptr;
-        // setting 1 (default): only launches WITHOUT a full round are split -- there the units replace the launch, no
-        // second kernel; setting 2: also the partial round behind full rounds, as a second launch
-        if (p >= 2 && (split_on >= 2 || full == 0) &&
-            split_scratch((hipStream_t)stream, cus2, &ws, &tk) == 0) {
-          parts = p;
-          a.items = (int)full;
-          a.full_items = (int)full;
-          a.split_parts = p;
-          a.split_ws = (float*)ws;
-          a.split_tickets = tk;
-          grid = cus2;
-        } else {
-          tail = 0;
-        }
-      }
-      const dim3 g3((unsigned)grid), b3(kBlock);
-      if (a.items > 0) {
-        if (use_pairs && half) hipLaunchKernelGGL((wino_conv_z_kernel<true, true>), g3, b3, 0, (hipStream_t)stream, a);
-        else if (use_pairs) hipLaunchKernelGGL((wino_conv_z_kernel<true, false>), g3, b3, 0, (hipStream_t)stream, a);
-        else if (half) hipLaunchKernelGGL((wino_conv_z_kernel<false, true>), g3, b3, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((wino_conv_z_kernel<false, false>), g3, b3, 0, (hipStream_t)stream, a);
-      }
-      if (parts) {
-        const dim3 t3((unsigned)(tail * parts));
-        if (use_pairs) hipLaunchKernelGGL((wino_conv_z_kernel<true, false, true>), t3, b3, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((wino_conv_z_kernel<false, false, true>), t3, b3, 0, (hipStream_t)stream, a);
-      }
+    if (t.parts) {
+      const dim3 t3((unsigned)(t.tail * t.parts));
+      if (use_pairs) hipLaunchKernelGGL((wino_conv_z_kernel<true, false, true>), t3, b3, 0, st, a);
+      else hipLaunchKernelGGL((wino_conv_z_kernel<false, false, true>), t3, b3, 0, st, a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+    return (int)hipGetLastError();
+  });
 }
 
 #ifdef WINO_TIMELINE

@@ -29,8 +29,15 @@
 
 #include "conv_internal.h"
 #include "ssad_kernels.h"
+#include "wino_launch.h"
 
 namespace {
+
+// shared with the F(2x2) engine and the launch planner (wino_launch.h): the 8 x 16 output patch (here 4 x 4 tiles of
+// 2 x 4 pixels), the 8 x 8 sub-patch (4 x 2 tiles), the level and work-item records
+using ssad_wino::PR; using ssad_wino::PC; using ssad_wino::SP; using ssad_wino::BM; using ssad_wino::KC;
+using ssad_wino::ZNT; using ssad_wino::kBlock; using ssad_wino::kNoSub; using ssad_wino::kOOBOff;
+using ssad_wino::WLevel; using ssad_wino::WTile;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -44,28 +51,20 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define W24_ABLATE 0
 #endif
 
-constexpr int KC = 16;                   // input channels per chunk
-constexpr int KS = KC / 4;               // MFMA k-steps per chunk
+constexpr int KS = KC / 4;               // MFMA k-steps per chunk of KC input channels
 constexpr int XQ = 6;                    // column positions of the transformed tile (F(4,3): 6)
 constexpr int XI = 4 * XQ;               // products per tile: 4 row positions x 6 column positions
 constexpr int STEPS = KS * XQ;           // A-stream float4 per lane per chunk = MFMA steps of 4
-constexpr int PR = 8, PC = 16;           // output patch (4 x 4 tiles of 2 x 4 pixels)
-constexpr int SP = 8;                    // sub-patch edge (4 x 2 tiles)
-constexpr int kBlock = 512;
-constexpr int BM = 128;
 constexpr int ZP = 40;                   // raw row pitch (two channels side by side, 20 columns each)
 constexpr int ZCP = (PR + 2) * ZP;       // floats per channel pair
 constexpr int ZRAW = (KC / 2) * ZCP;     // 3200 floats = 50 wave-loads
 constexpr int ZL = 7;                    // wave-loads per wave per chunk
 constexpr int ZRAWP = 8 * ZL * 64;       // padded raw buffer
 constexpr int NRAW = 3;
-constexpr int ZNT = 256;                 // work items per workgroup in the LDS list
 constexpr int AD = 8;                    // filter operand ring depth (steps)
 constexpr int VP = 16;                   // V row: the 16 tiles of one (product, channel)
 constexpr int VBUF = XI * KC * VP;       // transformed floats per buffer (24 KB)
-constexpr unsigned kOOBOff = 0x80000000u;
-constexpr int kNoSub = 1 << 24;
-static_assert(STEPS == 24 && AD == 8 && ZL == 7, "the counted waits below are written for these");
+static_assert(KC == 16 && STEPS == 24 && AD == 8 && ZL == 7, "the counted waits below are written for these");
 
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 using ssad_dev::uniform_rsrc;
@@ -126,26 +125,12 @@ __global__ void wino24_pack_multi_kernel(const PackTable t) {
   }
 }
 
-struct WLevel {
-  const float* x;
-  float* y;
-  const float* aux;                      // SSAD_CONV_MASK_AUX: the forward output whose sign masks y (fused ReluGradient)
-  const float* packed;
-  const float* bias;
-  int N, H, W;
-  int tiles_x, tiles_y, block_start;     // 8 x 16 patches
-  int sub_x, sub_y, pair_start;          // pairs of 8 x 8 sub-patches
-};
 struct WArgs {
   WLevel lv[SSAD_MAX_CONV_PROBLEMS];
   int n_levels;
   int M, K, chunks, flags;
   int patches, mblocks, items;
   int xcd_group;
-};
-struct WTile {
-  int l, mb;
-  int n[2], y0[2], x0[2];
 };
 
 // See wino_conv_z_kernel (conv3x3_winograd.hip) for the skeleton and how it got there; what differs is marked F24.
@@ -563,15 +548,6 @@ __global__ __launch_bounds__(kBlock, 1) void wino24_conv_kernel(const WArgs args
   }
 }
 
-// same rule as the F(2x2) kernel's launcher: sub-patch pairs where they save >= 4 % of the computed pixels
-bool level_wants_pairs(int H, int W) {
-  static const int geom = [] { const char* e = getenv("SSAD_WINO_PAIRS"); return (e && *e) ? atoi(e) : -1; }();
-  if (geom >= 0) return geom != 0;
-  const long long by_patch = (long long)cdiv(W, PC) * cdiv(H, PR) * 128;
-  const long long by_sub = (long long)cdiv(W, SP) * cdiv(H, SP) * 64;
-  return by_sub * 100 <= by_patch * 96;
-}
-
 }  // namespace
 
 extern "C" {
@@ -581,80 +557,49 @@ size_t ssad_conv_wino24_filter_floats(int M, int K) {
 }
 
 int ssad_conv_wino24_pack_filters(const ssad_pack_entry* entries_host, int n_entries, ssad_stream_t stream) {
-  if (n_entries < 0 || (n_entries > 0 && !entries_host)) return SSAD_E_BADARG;
-  for (int base = 0; base < n_entries; base += SSAD_MAX_PACK_ENTRIES) {
-    const int cnt = n_entries - base < SSAD_MAX_PACK_ENTRIES ? n_entries - base : SSAD_MAX_PACK_ENTRIES;
-    PackTable t;
+  return ssad_for_pack_chunks<PackTable>(entries_host, n_entries, /*need_dst=*/true, [&](const PackTable& t, int cnt) {
     size_t nmax = 0;
     bool any_dgrad = false;
     for (int i = 0; i < cnt; ++i) {
-      const ssad_pack_entry& e = entries_host[base + i];
-      if (e.Cout <= 0 || e.Cin <= 0 || !e.w || (!e.packed_fwd && !e.packed_dgrad)) return SSAD_E_BADARG;
-      t.e[i] = e;
+      const ssad_pack_entry& e = t.e[i];
       const size_t nf = ssad_conv_wino24_filter_floats(e.Cout, e.Cin), nd = ssad_conv_wino24_filter_floats(e.Cin, e.Cout);
       nmax = nf > nmax ? nf : nmax;
       if (e.packed_dgrad) { nmax = nd > nmax ? nd : nmax; any_dgrad = true; }
     }
-    for (int i = cnt; i < SSAD_MAX_PACK_ENTRIES; ++i) t.e[i] = ssad_pack_entry{};
     size_t bx = (nmax + 255) / 256;
     if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(wino24_pack_multi_kernel, dim3((unsigned)bx, (unsigned)cnt, any_dgrad ? 2u : 1u), dim3(256), 0,
                        (hipStream_t)stream, t);
-  }
-  return (int)hipGetLastError();
+  });
 }
 
 int ssad_conv3x3_forward_wino24(const ssad_conv_level* lv, int n_levels, const float* packed, const float* bias,
                                 int Cout, int Cin, int flags, ssad_stream_t stream) {
-  if (n_levels < 1 || n_levels > SSAD_MAX_CONV_PROBLEMS || Cout <= 0 || Cin <= 0) return SSAD_E_BADARG;
+  if (const int rc = ssad_wino::check_levels(lv, n_levels, packed, Cout, Cin, flags)) return rc;
+  // this engine only (the F(2x2) launcher takes these flags as they come): no Sigmoid under the mask; ACCUM_AUX needs
+  // the mask and no ReLU
   if ((flags & SSAD_CONV_MASK_AUX) && (flags & SSAD_CONV_SIGMOID)) return SSAD_E_BADARG;
   const bool accum = flags & SSAD_CONV_ACCUM_AUX;
   if (accum && (!(flags & SSAD_CONV_MASK_AUX) || (flags & SSAD_CONV_RELU))) return SSAD_E_BADARG;
-  for (int l = 0; l < n_levels; ++l) {
-    if (!(lv[l].packed ? lv[l].packed : packed)) return SSAD_E_BADARG;
-    if ((flags & SSAD_CONV_MASK_AUX) && !lv[l].aux) return SSAD_E_BADARG;
-    if (lv[l].N < 0 || lv[l].H < 0 || lv[l].W < 0) return SSAD_E_BADARG;
-    if ((long long)lv[l].N * lv[l].H * lv[l].W * (Cin > Cout ? Cin : Cout) >= (1LL << 29)) return SSAD_E_BADARG;
-  }
+  const hipStream_t st = (hipStream_t)stream;
+  WArgs a;
+  a.M = Cout; a.K = Cin; a.chunks = cdiv(Cin, KC); a.flags = flags;
+  a.mblocks = cdiv(Cout, BM);
+  a.xcd_group = 8;
+  // pass 0: the levels staged as 8 x 16 patches; pass 1: those staged as sub-patch pairs
   for (int pass = 0; pass < 2; ++pass) {
     const bool use_pairs = pass == 1;
-    WArgs a;
-    a.M = Cout; a.K = Cin; a.chunks = cdiv(Cin, KC); a.flags = flags;
-    a.mblocks = cdiv(Cout, BM);
-    int nl = 0;
-    long long blocks = 0, pairs = 0;
-    for (int l = 0; l < n_levels; ++l) {
-      if ((long long)lv[l].N * lv[l].H * lv[l].W == 0) continue;
-      if (level_wants_pairs(lv[l].H, lv[l].W) != use_pairs) continue;
-      WLevel& L = a.lv[nl++];
-      L.x = lv[l].x; L.y = lv[l].y; L.aux = lv[l].aux;
-      L.packed = lv[l].packed ? lv[l].packed : packed;
-      L.bias = lv[l].packed ? lv[l].bias : bias;
-      L.N = lv[l].N; L.H = lv[l].H; L.W = lv[l].W;
-      L.tiles_x = cdiv(L.W, PC); L.tiles_y = cdiv(L.H, PR);
-      L.block_start = (int)blocks;
-      blocks += (long long)L.N * L.tiles_x * L.tiles_y;
-      L.sub_x = cdiv(L.W, SP); L.sub_y = cdiv(L.H, SP);
-      L.pair_start = (int)pairs;
-      pairs += ((long long)L.N * L.sub_x * L.sub_y + 1) / 2;
-      if (blocks >= (1LL << 31)) return SSAD_E_BADARG;
-    }
-    if (nl == 0) continue;
-    a.n_levels = nl;
-    for (int l = nl; l < SSAD_MAX_CONV_PROBLEMS; ++l) a.lv[l] = WLevel{};
-    const int cus = ssad_cu_count();
-    a.patches = (int)(use_pairs ? pairs : blocks);
-    const long long total = (long long)a.patches * a.mblocks;
-    if (total >= (1LL << 31)) return SSAD_E_BADARG;
-    a.items = (int)total;
-    long long grid = total < cus ? total : cus;
-    if (grid * ZNT < total) grid = (total + ZNT - 1) / ZNT;
-    a.xcd_group = 8;
-    if (accum) {
-      if (use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true, true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((wino24_conv_kernel<false, true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
-    } else if (use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((wino24_conv_kernel<false>), dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, a);
+    const ssad_wino::Pass p = ssad_wino::plan_pass(lv, n_levels, packed, bias, use_pairs, a.mblocks, ssad_cu_count(), a.lv);
+    if (p.rc) return p.rc;
+    if (p.nl == 0) continue;
+    a.n_levels = p.nl;
+    a.patches = (int)(use_pairs ? p.pairs : p.blocks);
+    a.items = (int)p.total;
+    const dim3 g3((unsigned)p.grid), b3(kBlock);
+    if (accum && use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true, true>), g3, b3, 0, st, a);
+    else if (accum) hipLaunchKernelGGL((wino24_conv_kernel<false, true>), g3, b3, 0, st, a);
+    else if (use_pairs) hipLaunchKernelGGL((wino24_conv_kernel<true>), g3, b3, 0, st, a);
+    else hipLaunchKernelGGL((wino24_conv_kernel<false>), g3, b3, 0, st, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }

@@ -39,6 +39,27 @@ inline int ssad_cu_count() {
   return n;
 }
 
+// A table of ssad_pack_entry in chunks of SSAD_MAX_PACK_ENTRIES, for the pack launchers of the fp32 3x3 engines:
+// each chunk is checked, copied into a `Table` (a kernel argument: `ssad_pack_entry e[SSAD_MAX_PACK_ENTRIES]`, the rest
+// zeroed) and handed to `launch(table, entries in it)`.  need_dst: an entry with neither destination is refused.
+// A bad entry ends the walk with SSAD_E_BADARG; the chunks before it have been launched.
+template <class Table, class Launch>
+inline int ssad_for_pack_chunks(const ssad_pack_entry* entries_host, int n_entries, bool need_dst, Launch launch) {
+  if (n_entries < 0 || (n_entries > 0 && !entries_host)) return SSAD_E_BADARG;
+  for (int base = 0; base < n_entries; base += SSAD_MAX_PACK_ENTRIES) {
+    const int cnt = n_entries - base < SSAD_MAX_PACK_ENTRIES ? n_entries - base : SSAD_MAX_PACK_ENTRIES;
+    Table t;
+    for (int i = 0; i < cnt; ++i) {
+      const ssad_pack_entry& e = entries_host[base + i];
+      if (e.Cout <= 0 || e.Cin <= 0 || !e.w || (need_dst && !e.packed_fwd && !e.packed_dgrad)) return SSAD_E_BADARG;
+      t.e[i] = e;
+    }
+    for (int i = cnt; i < SSAD_MAX_PACK_ENTRIES; ++i) t.e[i] = ssad_pack_entry{};
+    launch(t, cnt);
+  }
+  return (int)hipGetLastError();
+}
+
 namespace ssad_dev {
 
 // Buffer descriptor from values the compiler must treat as wave-uniform: every

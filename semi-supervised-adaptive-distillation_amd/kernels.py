@@ -858,80 +858,88 @@ def momentum_sgd_update_(w, g, m, lr, momentum=0.9, weight_decay=1e-4, is_bias=F
 # conv 3x3
 # ---------------------------------------------------------------------------
 
-def conv_pack_filter(w, want_fwd=True, want_dgrad=True, out=None):
-    """w: Cout x Cin x 3 x 3.  Returns (packed_fwd, packed_dgrad)."""
-    L = lib()
+def _pack_3x3(w, size, launch, what, *, table, pair, want_fwd=True, want_dgrad=True, out=None):
+    """The fp32 3x3 *_pack_filter wrappers.  size: (M, K) -> floats of a pack; launch: the engine's single-filter
+    launcher, or (table) its ssad_pack_entry table launcher, given one entry.  out = (forward, data-gradient) packs to
+    fill, either may be None where the launcher allows it, decides instead of want_*.  Returns (pf, pd) -- pair -- or
+    pf alone unless there is a data-gradient pack."""
     _f32c(w, "filter")
     Cout, Cin, kh, kw = w.shape
     if (kh, kw) != (3, 3):
         raise KernelError("only 3x3 filters")
-    pf = torch.empty(L.ssad_conv_packed_filter_floats(Cout, Cin), dtype=torch.float32,
-                     device="cuda") if want_fwd and out is None else None
-    pd = torch.empty(L.ssad_conv_packed_filter_floats(Cin, Cout), dtype=torch.float32,
-                     device="cuda") if want_dgrad and out is None else None
-    if out is not None:         # (packed_fwd, packed_dgrad) to fill, either may be None; decides instead of want_*
+    if out is not None:
         pf, pd = out
-    _check(L.ssad_conv_pack_filter(_ptr(w), Cout, Cin, _ptr(pf), _ptr(pd), _stream()),
-           "conv_pack_filter")
-    return pf, pd
+    else:
+        pf = torch.empty(size(Cout, Cin), dtype=torch.float32, device="cuda") if want_fwd else None
+        pd = torch.empty(size(Cin, Cout), dtype=torch.float32, device="cuda") if want_dgrad else None
+    if table:
+        tab = (PackEntry * 1)(PackEntry(w.data_ptr(), Cout, Cin, pf.data_ptr(), pd.data_ptr() if pd is not None else 0))
+        _check(launch(tab, 1, _stream()), what)
+    else:
+        _check(launch(_ptr(w), Cout, Cin, _ptr(pf), _ptr(pd), _stream()), what)
+    return (pf, pd) if pair or pd is not None else pf
+
+
+def conv_pack_filter(w, want_fwd=True, want_dgrad=True, out=None):
+    """w: Cout x Cin x 3 x 3.  Returns (packed_fwd, packed_dgrad)."""
+    L = lib()
+    return _pack_3x3(w, L.ssad_conv_packed_filter_floats, L.ssad_conv_pack_filter, "conv_pack_filter", table=False,
+                     pair=True, want_fwd=want_fwd, want_dgrad=want_dgrad, out=out)
 
 
 def conv_wino_pack_filter(w, want_fwd=True, want_dgrad=True, out=None):
     """Winograd-domain filters U = G g G^T in MFMA operand order: (fwd, dgrad)."""
     L = lib()
-    _f32c(w, "filter")
-    Cout, Cin, kh, kw = w.shape
-    if (kh, kw) != (3, 3):
-        raise KernelError("only 3x3 filters")
-    pf = torch.empty(L.ssad_conv_wino_filter_floats(Cout, Cin), dtype=torch.float32,
-                     device="cuda") if want_fwd and out is None else None
-    pd = torch.empty(L.ssad_conv_wino_filter_floats(Cin, Cout), dtype=torch.float32,
-                     device="cuda") if want_dgrad and out is None else None
-    if out is not None:         # (packed_fwd, packed_dgrad) to fill, either may be None; decides instead of want_*
-        pf, pd = out
-    _check(L.ssad_conv_wino_pack_filter(_ptr(w), Cout, Cin, _ptr(pf), _ptr(pd), _stream()),
-           "conv_wino_pack_filter")
-    return pf, pd
+    return _pack_3x3(w, L.ssad_conv_wino_filter_floats, L.ssad_conv_wino_pack_filter, "conv_wino_pack_filter",
+                     table=False, pair=True, want_fwd=want_fwd, want_dgrad=want_dgrad, out=out)
 
 
 def conv_wino24_pack_filter(w, want_dgrad=False, out=None):
     """F(2x4, 3x3) filter pack U = G2 g G4^T; want_dgrad: -> (forward, data-gradient) packs (the latter of the
     flipped, transposed filter, Cin x Cout)."""
     L = lib()
-    _f32c(w, "filter")
-    Cout, Cin, kh, kw = w.shape
-    if (kh, kw) != (3, 3):
-        raise KernelError("only 3x3 filters")
-    if out is not None:         # (forward, data-gradient or None) to fill; decides instead of want_dgrad
-        pf, pd = out
-        want_dgrad = pd is not None
-    else:
-        pf = torch.empty(L.ssad_conv_wino24_filter_floats(Cout, Cin), dtype=torch.float32, device="cuda")
-        pd = torch.empty(L.ssad_conv_wino24_filter_floats(Cin, Cout), dtype=torch.float32,
-                         device="cuda") if want_dgrad else None
-    tab = (PackEntry * 1)(PackEntry(w.data_ptr(), Cout, Cin, pf.data_ptr(), pd.data_ptr() if want_dgrad else 0))
-    _check(L.ssad_conv_wino24_pack_filters(tab, 1, _stream()), "conv_wino24_pack_filters")
-    return (pf, pd) if want_dgrad else pf
+    return _pack_3x3(w, L.ssad_conv_wino24_filter_floats, L.ssad_conv_wino24_pack_filters, "conv_wino24_pack_filters",
+                     table=True, pair=False, want_dgrad=want_dgrad, out=out)
 
 
 def conv_split_pack_filter(w, want_dgrad=False, out=None):
     """Split-operand (3 x fp16 MFMA) filter pack: header with the filter's |max| + hi / lo fp16 planes; want_dgrad:
     -> (forward, data-gradient) packs (conv3x3_split.hip)."""
     L = lib()
-    _f32c(w, "filter")
-    Cout, Cin, kh, kw = w.shape
-    if (kh, kw) != (3, 3):
-        raise KernelError("only 3x3 filters")
-    if out is not None:         # (forward, data-gradient or None) to fill; decides instead of want_dgrad
-        pf, pd = out
-        want_dgrad = pd is not None
-    else:
-        pf = torch.empty(L.ssad_conv_split_filter_floats(Cout, Cin), dtype=torch.float32, device="cuda")
-        pd = torch.empty(L.ssad_conv_split_filter_floats(Cin, Cout), dtype=torch.float32,
-                         device="cuda") if want_dgrad else None
-    tab = (PackEntry * 1)(PackEntry(w.data_ptr(), Cout, Cin, pf.data_ptr(), pd.data_ptr() if want_dgrad else 0))
-    _check(L.ssad_conv_split_pack_filters(tab, 1, _stream()), "conv_split_pack_filters")
-    return (pf, pd) if want_dgrad else pf
+    return _pack_3x3(w, L.ssad_conv_split_filter_floats, L.ssad_conv_split_pack_filters, "conv_split_pack_filters",
+                     table=True, pair=False, want_dgrad=want_dgrad, out=out)
+
+
+def _conv_levels(xs, ys, auxs, packs=None, biases=None):
+    n = len(xs)
+    arr = (ConvLevel * n)()
+    for i in range(n):
+        N, _, H, W = xs[i].shape
+        arr[i] = ConvLevel(xs[i].data_ptr(),
+                           ys[i].data_ptr() if ys is not None and ys[i] is not None else 0,
+                           auxs[i].data_ptr() if auxs is not None and auxs[i] is not None else 0,
+                           N, H, W,
+                           packs[i].data_ptr() if packs is not None else 0,
+                           biases[i].data_ptr() if biases is not None and biases[i] is not None else 0)
+    return arr
+
+
+def _forward_3x3(launch, what, xs, packed, bias, Cout, *, relu, sigmoid, out, mask_by, flags=0, packs=None,
+                 biases=None, checked=True, tail=None):
+    """The fp32 3x3 forward wrappers: one launch over the levels xs (outputs: out, or fresh tensors).  mask_by: one mask
+    per level, the data-gradient form (CONV_MASK_AUX).  packs / biases: per level, for levels that do not share
+    `packed` / `bias`.  tail: (level table, Cin) -> the launcher's arguments between the flags and the stream."""
+    if checked:
+        for x in xs:
+            _f32c(x, "conv input")
+    Cin = xs[0].shape[1]
+    ys = out if out is not None else [
+        torch.empty((x.shape[0], Cout, x.shape[2], x.shape[3]), dtype=torch.float32, device="cuda") for x in xs]
+    flags |= (CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0) | (CONV_MASK_AUX if mask_by is not None else 0)
+    arr = _conv_levels(xs, ys, mask_by, packs, biases)
+    more = tail(arr, Cin) if tail is not None else ()
+    _check(launch(arr, len(xs), _ptr(packed), _ptr(bias), Cout, Cin, flags, *more, _stream()), what)
+    return ys
 
 
 def conv3x3_forward_split(xs, packed, bias, Cout, *, relu=False, sigmoid=False, out=None, mask_by=None, workspace=None,
@@ -939,19 +947,12 @@ def conv3x3_forward_split(xs, packed, bias, Cout, *, relu=False, sigmoid=False, 
     """conv3x3_forward on the split-operand engine (fp32 operands as hi + lo fp16, three fp16 MFMAs per pair, fp32
     accumulation; xs: levels sharing the filter).  mask_by: the data-gradient form, as conv3x3_forward_wino24."""
     L = lib()
-    for x in xs:
-        _f32c(x, "conv input")
-    Cin = xs[0].shape[1]
-    ys = out if out is not None else [
-        torch.empty((x.shape[0], Cout, x.shape[2], x.shape[3]), dtype=torch.float32, device="cuda") for x in xs]
-    flags = (CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0) | (CONV_MASK_AUX if mask_by is not None else 0)
-    arr = _conv_levels(xs, ys, mask_by)
-    need = L.ssad_conv3x3_split_workspace_bytes(arr, len(xs), Cin)
-    workspace = _own_workspace(workspace, need)
-    _check(L.ssad_conv3x3_forward_split(arr, len(xs), _ptr(packed), _ptr(bias), Cout, Cin, flags, _ptr(workspace),
-                                        workspace.numel(), _ptr(amax_in), _ptr(amax_out), _stream()),
-           "conv3x3_forward_split")
-    return ys
+
+    def tail(arr, Cin):
+        ws = _own_workspace(workspace, L.ssad_conv3x3_split_workspace_bytes(arr, len(xs), Cin))
+        return _ptr(ws), ws.numel(), _ptr(amax_in), _ptr(amax_out)
+    return _forward_3x3(L.ssad_conv3x3_forward_split, "conv3x3_forward_split", xs, packed, bias, Cout, relu=relu,
+                        sigmoid=sigmoid, out=out, mask_by=mask_by, tail=tail)
 
 
 def conv3x3_split_items(shapes, Cout):
@@ -971,32 +972,8 @@ def conv3x3_forward_wino24(xs, packed, bias, Cout, *, relu=False, sigmoid=False,
     accumulate (with mask_by and out): y = mask > 0 ? y + out : 0, out read before it is overwritten."""
     if accumulate and (mask_by is None or out is None):
         raise KernelError("conv3x3_forward_wino24: accumulate=True needs mask_by= and out=")
-    L = lib()
-    for x in xs:
-        _f32c(x, "conv input")
-    Cin = xs[0].shape[1]
-    ys = out if out is not None else [
-        torch.empty((x.shape[0], Cout, x.shape[2], x.shape[3]), dtype=torch.float32, device="cuda") for x in xs]
-    flags = (CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0) | (CONV_MASK_AUX if mask_by is not None else 0)
-    flags |= CONV_ACCUM_AUX if accumulate else 0
-    arr = _conv_levels(xs, ys, mask_by)
-    _check(L.ssad_conv3x3_forward_wino24(arr, len(xs), _ptr(packed), _ptr(bias), Cout, Cin, flags, _stream()),
-           "conv3x3_forward_wino24")
-    return ys
-
-
-def _conv_levels(xs, ys, auxs, packs=None, biases=None):
-    n = len(xs)
-    arr = (ConvLevel * n)()
-    for i in range(n):
-        N, _, H, W = xs[i].shape
-        arr[i] = ConvLevel(xs[i].data_ptr(),
-                           ys[i].data_ptr() if ys is not None and ys[i] is not None else 0,
-                           auxs[i].data_ptr() if auxs is not None and auxs[i] is not None else 0,
-                           N, H, W,
-                           packs[i].data_ptr() if packs is not None else 0,
-                           biases[i].data_ptr() if biases is not None and biases[i] is not None else 0)
-    return arr
+    return _forward_3x3(lib().ssad_conv3x3_forward_wino24, "conv3x3_forward_wino24", xs, packed, bias, Cout, relu=relu,
+                        sigmoid=sigmoid, out=out, mask_by=mask_by, flags=CONV_ACCUM_AUX if accumulate else 0)
 
 
 def conv3x3_forward(xs, packed, bias, Cout, *, relu=False, sigmoid=False, mask_by=None,
@@ -1004,19 +981,8 @@ def conv3x3_forward(xs, packed, bias, Cout, *, relu=False, sigmoid=False, mask_b
     """xs: list of N x Cin x H x W tensors (FPN levels sharing the filter).
     Returns the list of N x Cout x H x W outputs (one launch for all levels)."""
     L = lib()
-    for x in xs:
-        _f32c(x, "conv input")
-    Cin = xs[0].shape[1]
-    ys = out if out is not None else [
-        torch.empty((x.shape[0], Cout, x.shape[2], x.shape[3]), dtype=torch.float32,
-                    device="cuda") for x in xs]
-    flags = ((CONV_RELU if relu else 0) | (CONV_MASK_AUX if mask_by is not None else 0)
-             | (CONV_SIGMOID if sigmoid else 0))
-    arr = _conv_levels(xs, ys, mask_by)
-    fn = L.ssad_conv3x3_forward_wino if wino else L.ssad_conv3x3_forward
-    _check(fn(arr, len(xs), _ptr(packed), _ptr(bias), Cout, Cin, flags, _stream()),
-           "conv3x3_forward")
-    return ys
+    return _forward_3x3(L.ssad_conv3x3_forward_wino if wino else L.ssad_conv3x3_forward, "conv3x3_forward", xs, packed,
+                        bias, Cout, relu=relu, sigmoid=sigmoid, out=out, mask_by=mask_by)
 
 
 def conv3x3_forward_multi(problems, Cout, *, relu=False, sigmoid=False, wino=False):
@@ -1034,13 +1000,9 @@ def conv3x3_forward_multi(problems, Cout, *, relu=False, sigmoid=False, wino=Fal
     masked = [a is not None for a in auxs]
     if any(masked) and not all(masked):
         raise KernelError("either every problem of a launch is masked or none")
-    Cin = xs[0].shape[1]
-    flags = ((CONV_RELU if relu else 0) | (CONV_MASK_AUX if all(masked) and masked else 0)
-             | (CONV_SIGMOID if sigmoid else 0))
-    arr = _conv_levels(xs, ys, auxs, packs, biases)
-    fn = L.ssad_conv3x3_forward_wino if wino else L.ssad_conv3x3_forward
-    _check(fn(arr, len(xs), None, None, Cout, Cin, flags, _stream()), "conv3x3_forward_multi")
-    return ys
+    return _forward_3x3(L.ssad_conv3x3_forward_wino if wino else L.ssad_conv3x3_forward, "conv3x3_forward_multi", xs,
+                        None, None, Cout, relu=relu, sigmoid=sigmoid, out=ys, mask_by=auxs if any(masked) else None,
+                        packs=packs, biases=biases, checked=False)
 
 
 def conv3x3_wgrad(xs, dys, Cout, *, want_db=True, accumulate=False, dW=None, db=None, split=False, x_amax=None,
