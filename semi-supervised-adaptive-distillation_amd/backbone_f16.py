@@ -29,6 +29,7 @@ import torch
 from . import kernels as K
 from . import program as PR
 from .backbone_pipeline import NativeResNetFPN, ARCHS, GROUPED
+from .engines import emit_conv3x3_f16, emit_conv3x3_wgrad_f16, emit_f16_packs
 
 KL_PW, KL_C3, KL_W3, KL_W1, KL_GR, KL_EW, KL_PACK = 57, 58, 59, 60, 61, 62, 63
 
@@ -85,30 +86,15 @@ class NativeResNetFPNF16(NativeResNetFPN):
     def _c3(self, P, probs, Cin, Cout, flags):
         """probs: [(x, y, mask or None, packed, bias or None)]: independent 3x3 convolutions of one
         (Cin, Cout) in one launch (conv3x3_f16_kernel)."""
-        arr = (K.F16Level * len(probs))()
-        for i, (x, y, mask, packed, bias) in enumerate(probs):
-            arr[i].x, arr[i].y = x.data_ptr(), y.data_ptr()
-            arr[i].aux = mask.data_ptr() if mask is not None else None
-            arr[i].N, arr[i].H, arr[i].W = x.shape[0], x.shape[2], x.shape[3]
-            arr[i].packed = packed.data_ptr()
-            arr[i].bias = bias.data_ptr() if bias is not None else None
-        px = sum(p[0].shape[0] * p[0].shape[2] * p[0].shape[3] for p in probs)
-        P.add(PR.F16_CONV3X3, KL_C3, i=(len(probs), Cin, Cout, flags), p=(arr, None, None),
-              work=2.0 * 9 * Cout * Cin * px, keep=[t for p in probs for t in p if t is not None])
+        emit_conv3x3_f16(P, KL_C3, probs, Cin, Cout, flags)
 
     def _ew16(self, P, mode, a, b, y, Cc, stride=1, acc=0):
         P.add(PR.F16_EW, KL_EW, i=(mode, y.shape[0], Cc, y.shape[2], y.shape[3], stride, acc), p=(a, b, y),
               work=2.0 * (y.numel() + a.numel() + (b.numel() if b is not None else 0)))
 
     def _wg3(self, P, x, dy, layer):
-        arr = (K.F16WgradLevel * 1)()
-        arr[0].x, arr[0].dy = x.data_ptr(), dy.data_ptr()
-        arr[0].N, arr[0].H, arr[0].W = x.shape[0], x.shape[2], x.shape[3]
-        nb = K.lib().ssad_conv3x3_wgrad_f16_levels_workspace_bytes(arr, 1, layer.cin, layer.cout)
-        stream, ws = self._aux(P)
-        P.add(PR.F16_WGRAD, KL_W3, i=(1, layer.cin, layer.cout, 0), f=(1.0,), l=(nb,),
-              p=(arr, self.inv_scale, layer.gw, layer.gb, ws.need(nb)),
-              work=2.0 * 9 * layer.cout * layer.cin * x.shape[0] * x.shape[2] * x.shape[3], keep=[x, dy], stream=stream)
+        emit_conv3x3_wgrad_f16(P, KL_W3, [x], [dy], layer.gw, layer.gb, layer.cin, layer.cout, self.inv_scale,
+                               self._aux)
 
     def _wg1(self, P, x, dy, layer):
         N, H, W = x.shape[0], x.shape[2], x.shape[3]
@@ -150,17 +136,7 @@ class NativeResNetFPNF16(NativeResNetFPN):
                 tgt.add(PR.TRANSPOSE_FILTER, 54, i=(l.cout, l.cin * l.k * l.k, l.cout), p=(l.w, l.wt),
                         work=8.0 * l.w.numel())
         for train, tgt in ((True, P), (False, prep)):
-            ents = packs[train]
-            if not ents:
-                continue
-            tab = (K.F16PackEntry * len(ents))()
-            for i, (w, wf, wd, M, Cc, taps) in enumerate(ents):
-                tab[i] = K.F16PackEntry(w.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None,
-                                        M, Cc, taps, 0)
-            tgt.add(PR.F16_PACK_FILTERS, KL_PACK, i=(len(ents),), p=(tab,),
-                    work=sum(4.0 * w.numel() + 2.0 * (wf.numel() + (wd.numel() if wd is not None else 0))
-                             for (w, wf, wd, M, Cc, taps) in ents),
-                    keep=[t for e in ents for t in e[:3] if t is not None])
+            emit_f16_packs(tgt, KL_PACK, packs[train])
         prep.build()
         self._packed_frozen = False
         P.mark("forward")

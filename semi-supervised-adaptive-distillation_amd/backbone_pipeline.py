@@ -43,7 +43,7 @@ from . import kernels as K
 from . import program as PR
 from .data_parallel import BucketedAllReduce
 from .engines import (AmaxTable, Engine, Switches, backbone_engine, backbone_wgrad_split, emit_conv3x3,
-                      emit_conv3x3_wgrad, emit_packs, filter_floats, same_engine)
+                      emit_conv3x3_wgrad, emit_packs, emit_sgd_flat, filter_floats, same_engine)
 from .modeling.resnet_fpn import ChannelRatioError, channel_widths
 
 # pixels (all images) a pointwise launch needs before the split-operand GEMM pays (see NativeResNetFPN._gemm)
@@ -434,10 +434,7 @@ class NativeResNetFPN(object):
 
     def _emit_grouped_packs(self, P, layers):
         """One GROUPED_PACKS record: the forward and data-gradient packs of every trained grouped layer."""
-        tab = (K.GroupedPackEntry * len(layers))()
-        for k, l in enumerate(layers):
-            tab[k] = K.GroupedPackEntry(l.w.data_ptr(), l.pf.data_ptr(), l.pd.data_ptr(), l.cout, l.group)
-        self._grouped_pack_table = tab
+        tab = self._grouped_pack_table = K.grouped_pack_entries([(l.w, l.pf, l.pd, l.cout, l.group) for l in layers])
         P.add(PR.GROUPED_PACKS, 77, i=(len(layers),), p=(tab,),
               work=4.0 * sum(l.w.numel() + l.pf.numel() + l.pd.numel() for l in layers),
               keep=[t for l in layers for t in (l.w, l.pf, l.pd)])
@@ -559,14 +556,8 @@ class NativeResNetFPN(object):
         self._split = PR.Workspace()
 
     def _emit_sgd(self, P):
-        tab = (K.SgdSegment * len(self.segments))()
-        for i, (off, n, isb, row_len, s2) in enumerate(self.segments):
-            tab[i] = K.SgdSegment(off, n, isb, row_len if s2 is not None else 0,
-                                  s2.data_ptr() if s2 is not None else None)
-        P.add(PR.SGD_FLAT, 55, i=(len(self.segments),), f=(self.momentum, self.weight_decay),
-              p=(self.params_flat, self.grads_flat, self.moms_flat, self.lr, tab, self.skip_flag),
-              work=4.0 * 6 * self.params_flat.numel(),
-              keep=[s2 for (_, _, _, _, s2) in self.segments if s2 is not None])
+        emit_sgd_flat(P, 55, self.segments, self.params_flat, self.grads_flat, self.moms_flat, self.lr, self.momentum,
+                      self.weight_decay, self.skip_flag)
 
     def _bind_workspaces(self):
         self.wss = {k: w.bind(self.device) for k, w in self._aux_ws.items()}

@@ -1,8 +1,10 @@
 """Which engine runs a 3x3 convolution of the native fp32 pipelines (head_pipeline.DistillHeads,
 backbone_pipeline.NativeResNetFPN): the engine type, the one read of the environment switches, the rules of each
-pipeline, the two tables (ssad_pack_entry[], ssad_conv_level[]) both pipelines hand to the kernels, the table of
-|max| words of the split-operand engines (AmaxTable) and the one emitter of each 3x3 launch record (emit_conv3x3,
-emit_conv3x3_wgrad).
+pipeline, the table of |max| words of the split-operand engines (AmaxTable) and the one emitter of each launch record
+the pipelines share: the 3x3 records and filter packs of the fp32 programs (emit_conv3x3, emit_conv3x3_wgrad,
+emit_packs), those of the fp16 ones (emit_conv3x3_f16, emit_conv3x3_wgrad_f16, emit_f16_packs) and the flat SGD update
+(emit_sgd_flat).  An emitter holds its record's slot order, work formula and keep list; the tables come from the
+builders of kernels.py.
 
 A pipeline reads the switches once, at construction, asks the rule for every convolution before it allocates
 anything, packs each filter in the layout of the planned engine and launches the planned engine on it.  DESIGN.md
@@ -153,14 +155,7 @@ def same_engine(engines):
     return engines.pop()
 
 
-def conv_table(rows):
-    """rows: [(x, y, aux, packed, bias)], tensors or None -> ssad_conv_level[]"""
-    arr = (K.ConvLevel * len(rows))()
-    for k, (x, y, aux, packed, bias) in enumerate(rows):
-        arr[k] = K.ConvLevel(x.data_ptr(), *[t.data_ptr() if t is not None else 0 for t in (y, aux)],
-                             x.shape[0], x.shape[2], x.shape[3],
-                             *[t.data_ptr() if t is not None else 0 for t in (packed, bias)])
-    return arr
+conv_table = K.conv_levels         # the name this table's builder had here
 
 
 def emit_packs(P, klass, packs, order):
@@ -173,10 +168,8 @@ def emit_packs(P, klass, packs, order):
             for (w, cout, cin, pf, pd), nbytes in zip(entries, moved):
                 P.add(PR.PACK_FILTER, klass, i=(cout, cin), p=(w, pf, pd), work=nbytes)
         elif entries:
-            tab = (K.PackEntry * len(entries))()
-            for k, (w, cout, cin, pf, pd) in enumerate(entries):
-                tab[k] = K.PackEntry(w.data_ptr(), cout, cin, *[t.data_ptr() if t is not None else 0 for t in (pf, pd)])
-            P.add(PR.WINO_PACK_FILTERS, klass, i=(len(entries), _PACK_LAYOUT[engine]), p=(tab,), work=sum(moved),
+            P.add(PR.WINO_PACK_FILTERS, klass, i=(len(entries), _PACK_LAYOUT[engine]), p=(K.pack_entries(entries),),
+                  work=sum(moved),
                   keep=[t for w, _, _, pf, pd in entries for t in (w, pf, pd) if t is not None])
 
 
@@ -226,18 +219,22 @@ class AmaxTable(object):
                 P.add(PR.SPLIT_ABSMAX, 73, p=(ts[0], self.addr(base)), l=(ts[0].numel(),), work=nbytes, stream=0)
             else:
                 if table is None:
-                    table, field = conv_table([(t, None, None, None, None) for t in ts]), 0
+                    table, field = K.conv_levels([(t, None, None, None, None) for t in ts]), 0
                 P.add(PR.SPLIT_ABSMAX_LEVELS, 73, i=(len(ts), channels, field), p=(table, self.addr(base)),
                       work=nbytes, keep=ts, stream=0)
         return base
 
 
+def _pixels(xs):
+    return sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
+
+
 def emit_conv3x3(P, klass, rows, cout, cin, flags, engine, amax, ws, levels=1, own_table=False, fold=True):
-    """One CONV3X3 record: independent convolutions of one (cout, cin) on one engine.  rows: conv_table()'s, `levels`
+    """One CONV3X3 record: independent convolutions of one (cout, cin) on one engine.  rows: K.conv_levels()'s, `levels`
     consecutive rows per problem.  The split-operand engine takes its workspace `ws`, the words of its inputs (found
     or measured: through its own table when own_table) and, when fold, fresh words its epilogue folds the outputs'
     |max| into.  -> (record index, table)"""
-    arr = conv_table(rows)
+    arr = K.conv_levels(rows)
     ptrs, sizes = (arr, None, None), ()
     if engine == Engine.SPLIT:
         nb = K.lib().ssad_conv3x3_split_workspace_bytes(arr, len(arr), cin)
@@ -245,9 +242,9 @@ def emit_conv3x3(P, klass, rows, cout, cin, flags, engine, amax, ws, levels=1, o
         xa = amax.addr(amax.measure(P, groups(0), cin, arr if own_table else None))
         ya = amax.addr(amax.reserve(groups(1))) if fold else None
         ptrs, sizes = (arr, None, None, ws.need(nb), xa, ya), (nb,)
-    px = sum(r[0].shape[0] * r[0].shape[2] * r[0].shape[3] for r in rows)
     return P.add(PR.CONV3X3, klass, i=(len(arr), cout, cin, flags, engine), l=sizes, p=ptrs,
-                 work=2.0 * 9 * cout * cin * px, keep=[t for r in rows for t in r if t is not None]), arr
+                 work=2.0 * 9 * cout * cin * _pixels(r[0] for r in rows),
+                 keep=[t for r in rows for t in r if t is not None]), arr
 
 
 def emit_conv3x3_wgrad(P, klasses, xs, dys, gw, gb, cout, cin, split, amax, fork, own_table=False):
@@ -255,7 +252,7 @@ def emit_conv3x3_wgrad(P, klasses, xs, dys, gw, gb, cout, cin, split, amax, fork
     split: the pipeline's rule wants the split-operand engine (a level of 2 GiB or more still goes to the exact
     one); klasses = (exact, split) timing classes.  The operands' words are found or measured on the main stream;
     then fork(P) emits the pipeline's fork and returns the record's (stream, Workspace).  -> (record index, table)"""
-    arr = conv_table([(x, None, dy, None, None) for x, dy in zip(xs, dys)])
+    arr = K.conv_levels([(x, None, dy, None, None) for x, dy in zip(xs, dys)])
     L = K.lib()
     nb = L.ssad_conv3x3_wgrad_split_workspace_bytes(arr, len(arr), cout, cin) if split else 0
     split = nb > 0
@@ -266,7 +263,42 @@ def emit_conv3x3_wgrad(P, klasses, xs, dys, gw, gb, cout, cin, split, amax, fork
     else:
         nb = L.ssad_conv3x3_wgrad_workspace_bytes(arr, len(arr), cout, cin)
     stream, ws = fork(P)
-    px = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xs)
     return P.add(PR.CONV3X3_WGRAD, klasses[split], i=(len(arr), cout, cin, 0, int(split)), l=(nb,),
-                 p=(arr, gw, gb, ws.need(nb), xa, da), work=2.0 * 9 * cout * cin * px, keep=list(xs) + list(dys),
-                 stream=stream), arr
+                 p=(arr, gw, gb, ws.need(nb), xa, da), work=2.0 * 9 * cout * cin * _pixels(xs),
+                 keep=list(xs) + list(dys), stream=stream), arr
+
+
+def emit_conv3x3_f16(P, klass, rows, cin, cout, flags):
+    """One F16_CONV3X3 record: independent fp16 convolutions of one (cin, cout), kernels.f16_levels()'s rows.
+    -> (record index, table)"""
+    arr = K.f16_levels(rows)
+    return P.add(PR.F16_CONV3X3, klass, i=(len(arr), cin, cout, flags), p=(arr, None, None),
+                 work=2.0 * 9 * cout * cin * _pixels(r[0] for r in rows),
+                 keep=[t for r in rows for t in r if t is not None]), arr
+
+
+def emit_conv3x3_wgrad_f16(P, klass, xs, dys, gw, gb, cin, cout, inv_scale, fork):
+    """One F16_WGRAD record over the levels xs / dys that share the filter gradient gw (+ bias gradient gb), both times
+    the device scalar inv_scale; fork(P) as for emit_conv3x3_wgrad.  -> (record index, table)"""
+    arr = K.f16_wgrad_levels(xs, dys)
+    nb = K.lib().ssad_conv3x3_wgrad_f16_levels_workspace_bytes(arr, len(arr), cin, cout)
+    stream, ws = fork(P)
+    return P.add(PR.F16_WGRAD, klass, i=(len(arr), cin, cout, 0), f=(1.0,), l=(nb,),
+                 p=(arr, inv_scale, gw, gb, ws.need(nb)), work=2.0 * 9 * cout * cin * _pixels(xs),
+                 keep=list(xs) + list(dys), stream=stream), arr
+
+
+def emit_f16_packs(P, klass, entries):
+    """One F16_PACK_FILTERS record: kernels.f16_pack_entries()'s entries in one launch; nothing for an empty list."""
+    if entries:
+        P.add(PR.F16_PACK_FILTERS, klass, i=(len(entries),), p=(K.f16_pack_entries(entries),),
+              work=sum(4.0 * e[0].numel() + 2.0 * sum(t.numel() for t in e[1:3] if t is not None) for e in entries),
+              keep=[t for e in entries for t in e[:3] if t is not None])
+
+
+def emit_sgd_flat(P, klass, segments, params, grads, moms, lr, momentum, weight_decay, skip_flag):
+    """One SGD_FLAT record: the momentum update of the flat buffers by kernels.sgd_segments()'s segments; skip_flag: a
+    device word that drops the update when it is set, or None."""
+    return P.add(PR.SGD_FLAT, klass, i=(len(segments),), f=(momentum, weight_decay),
+                 p=(params, grads, moms, lr, K.sgd_segments(segments), skip_flag), work=4.0 * 6 * params.numel(),
+                 keep=[s[4] for s in segments if s[4] is not None])

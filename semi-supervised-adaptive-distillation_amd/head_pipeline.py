@@ -34,8 +34,9 @@ from . import kernels as K
 from . import program as PR
 from . import synth
 from .data_parallel import BucketedAllReduce
-from .engines import (AmaxTable, Engine, Switches, emit_conv3x3, emit_conv3x3_wgrad, emit_packs, filter_floats,
-                      same_engine, subnet_engine, subnet_wgrad_split)
+from .engines import (AmaxTable, Engine, Switches, emit_conv3x3, emit_conv3x3_f16, emit_conv3x3_wgrad,
+                      emit_conv3x3_wgrad_f16, emit_f16_packs, emit_packs, emit_sgd_flat, filter_floats, same_engine,
+                      subnet_engine, subnet_wgrad_split)
 from .modeling.retinanet_heads import HeadConfig, retinanet_bias_init
 
 
@@ -261,7 +262,7 @@ class DistillHeads(object):
     @staticmethod
     def _rows(problems):
         """problems: [(xs, outs or None, masks or None, packed or None, bias or None)], one tensor per level in xs / outs /
-        masks -> engines.conv_table()'s rows, the problems' levels one after the other"""
+        masks -> kernels.conv_levels()'s rows, the problems' levels one after the other"""
         return [(x, outs[l] if outs is not None else None, masks[l] if masks is not None else None, packed, bias)
                 for xs, outs, masks, packed, bias in problems for l, x in enumerate(xs)]
 
@@ -587,16 +588,13 @@ class DistillHeads(object):
             P.mark("backward_late_done")
 
     # -- update -----------------------------------------------------------------------------------
-    def _emit_sgd(self, P):
-        specs = self.params.specs
-        tab = (K.SgdSegment * len(specs))()
-        for k, (name, shape, is_bias, _) in enumerate(specs):
-            tab[k] = K.SgdSegment(self.params.offsets[name], int(np.prod(shape)), int(is_bias), 0, None)
+    def _emit_sgd(self, P, skip_flag=None):
         if "sgd_update" not in P.marks:
             P.mark("sgd_update")            # fp32: nothing precedes the update ("sgd" == "sgd_update")
-        P.add(PR.SGD_FLAT, 11, i=(len(specs),), f=(self.momentum, self.weight_decay),
-              p=(self.params.flat, self.grads.flat, self.moms.flat, self.lr, tab, None),
-              work=4.0 * 6 * self.params.flat.numel())
+        emit_sgd_flat(P, 11, [(self.params.offsets[name], int(np.prod(shape)), is_bias, 0, None)
+                              for name, shape, is_bias, _ in self.params.specs],
+                      self.params.flat, self.grads.flat, self.moms.flat, self.lr, self.momentum, self.weight_decay,
+                      skip_flag)
         P.mark("ls_update")                 # fp32: nothing follows the update
 
     # -- input binding ------------------------------------------------------------------------------
@@ -810,7 +808,7 @@ class DistillHeadsF16(DistillHeads):
         return float(self.ls_state[0])
 
     def _alloc_packed(self, params, who):
-        """-> ({layer: (fwd, dgrad or None)}, what _emit_pack needs: here the list of ssad_f16_pack_entry fields)"""
+        """-> ({layer: (fwd, dgrad or None)}, what _emit_pack needs: here kernels.f16_pack_entries()'s entries)"""
         packed, ops, want_dgrad = {}, [], who == "student"
         for tower in ("cls", "bbox"):
             for name in self._layers(tower):
@@ -820,43 +818,15 @@ class DistillHeadsF16(DistillHeads):
                 wf = torch.empty(n, dtype=torch.float16, device=self.device)
                 wd = torch.empty(n, dtype=torch.float16, device=self.device) if want_dgrad else None
                 packed[name] = (wf, wd)
-                ops.append((w, M, Cc, wf, wd))
+                ops.append((w, wf, wd, M, Cc, 9))
         return packed, ops
 
     def _emit_pack(self, P, entries):
         """All of a network's filters in one launch (ssad_f16_pack_filters)."""
-        if not entries:
-            return
-        tab = (K.F16PackEntry * len(entries))()
-        for i, (w, M, Cc, wf, wd) in enumerate(entries):
-            tab[i] = K.F16PackEntry(w.data_ptr(), wf.data_ptr(), wd.data_ptr() if wd is not None else None, M, Cc, 9, 0)
-        P.add(PR.F16_PACK_FILTERS, 33, i=(len(entries),), p=(tab,),
-              work=sum(4.0 * w.numel() + 2.0 * (wf.numel() + (wd.numel() if wd is not None else 0))
-                       for w, M, Cc, wf, wd in entries),
-              keep=[t for e in entries for t in (e[0], e[3], e[4]) if t is not None])
-
-    def _f16_table(self, problems):
-        """problems: [(xs, outs, masks or None, packed or None, bias or None)] -> ssad_f16_level[]"""
-        n = sum(len(p[0]) for p in problems)
-        arr = (K.F16Level * n)()
-        k = 0
-        for xs, outs, masks, packed, bias in problems:
-            for l, xb in enumerate(xs):
-                arr[k].x, arr[k].y = xb.data_ptr(), outs[l].data_ptr()
-                arr[k].aux = masks[l].data_ptr() if masks is not None else None
-                arr[k].N, arr[k].H, arr[k].W = xb.shape[0], xb.shape[2], xb.shape[3]
-                arr[k].packed = packed.data_ptr() if packed is not None else None
-                arr[k].bias = bias.data_ptr() if bias is not None else None
-                k += 1
-        return arr
+        emit_f16_packs(P, 33, entries)
 
     def _emit_conv16(self, P, problems, Cin, Cout, flags, klass):
-        arr = self._f16_table(problems)
-        px = sum(x.shape[0] * x.shape[2] * x.shape[3] for p in problems for x in p[0])
-        P.add(PR.F16_CONV3X3, klass, i=(len(arr), Cin, Cout, flags), p=(arr, None, None),
-              work=2.0 * 9 * Cout * Cin * px,
-              keep=[t for p in problems for t in (list(p[0]) + list(p[1]) + list(p[2] or []))] +
-                   [t for p in problems for t in p[3:] if t is not None])
+        emit_conv3x3_f16(P, klass, self._rows(problems), Cin, Cout, flags)
 
     def _emit_forward(self, P):
         cfg, D = self.cfg, self.D
@@ -899,17 +869,8 @@ class DistillHeadsF16(DistillHeads):
                               D, A4, F32, 36)
 
     def _emit_wgrad16(self, P, xbs, dybs, name, Cin, Cout):
-        n = len(xbs)
-        arr = (K.F16WgradLevel * n)()
-        for l, (xb, dyb) in enumerate(zip(xbs, dybs)):
-            arr[l].x, arr[l].dy = xb.data_ptr(), dyb.data_ptr()
-            arr[l].N, arr[l].H, arr[l].W = xb.shape[0], xb.shape[2], xb.shape[3]
-        nb = K.lib().ssad_conv3x3_wgrad_f16_levels_workspace_bytes(arr, n, Cin, Cout)
-        px = sum(x.shape[0] * x.shape[2] * x.shape[3] for x in xbs)
-        stream, ws = self._fork(P)
-        P.add(PR.F16_WGRAD, 37, i=(n, Cin, Cout, 0), f=(1.0,), l=(nb,),
-              p=(arr, self.ls_state[1:2], self.grads[name + "_w"], self.grads[name + "_b"], ws.need(nb)),
-              work=2.0 * 9 * Cout * Cin * px, keep=list(xbs) + list(dybs), stream=stream)
+        emit_conv3x3_wgrad_f16(P, 37, xbs, dybs, self.grads[name + "_w"], self.grads[name + "_b"], Cin, Cout,
+                               self.ls_state[1:2], self._fork)
 
     def _emit_backward(self, P):
         cfg, D = self.cfg, self.D
@@ -958,9 +919,7 @@ class DistillHeadsF16(DistillHeads):
         n = self.grads.flat.numel()
         P.add(PR.CHECK_FINITE, 38, l=(n,), p=(self.grads.flat, self.ls_counters), work=4.0 * n)
         P.mark("sgd_update")
-        idx = len(P.ops)
-        DistillHeads._emit_sgd(self, P)
-        P.set_ptr(idx, 5, self.ls_counters)            # the update is skipped on overflow
+        DistillHeads._emit_sgd(self, P, self.ls_counters)          # the update is skipped on overflow
         P.add(PR.LOSS_SCALE_UPDATE, 38, i=(self.LOSS_SCALE_GROWTH_INTERVAL,),
               f=(2.0, 0.5, self.LOSS_SCALE_MIN, self.LOSS_SCALE_MAX), p=(self.ls_state, self.ls_counters))
 

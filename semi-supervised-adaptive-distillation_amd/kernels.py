@@ -855,6 +855,65 @@ def momentum_sgd_update_(w, g, m, lr, momentum=0.9, weight_decay=1e-4, is_bias=F
 
 
 # ---------------------------------------------------------------------------
+# descriptor tables: the ONE builder of each struct a launcher takes as an array.  Tensors (or None = NULL) in, the
+# ctypes array out; no device check, so the native programs build them over CPU tensors too.  The eager wrappers
+# validate their operands before they call a builder.
+# ---------------------------------------------------------------------------
+
+def _table(struct, rows):
+    return (struct * len(rows))(*[struct(*r) for r in rows])
+
+
+def _levels(struct, rows):
+    """rows: [(x, y, aux, packed, bias)]; N, H, W are dimensions 0, 2, 3 of x, NCHW or blocked [N][C/8][H][W][8]"""
+    return _table(struct, [(_ptr(x), _ptr(y), _ptr(aux), x.shape[0], x.shape[2], x.shape[3], _ptr(packed), _ptr(bias))
+                           for x, y, aux, packed, bias in rows])
+
+
+def conv_levels(rows):
+    """rows: [(x, y, aux, packed, bias)] -> ssad_conv_level[]"""
+    return _levels(ConvLevel, rows)
+
+
+def f16_levels(rows):
+    """rows: [(x, y, aux, packed, bias)] -> ssad_f16_level[]"""
+    return _levels(F16Level, rows)
+
+
+def f16_wgrad_levels(xs, dys):
+    """-> ssad_f16_wgrad_level[], one level per (x, dy)"""
+    return _table(F16WgradLevel, [(_ptr(x), _ptr(dy), x.shape[0], x.shape[2], x.shape[3]) for x, dy in zip(xs, dys)])
+
+
+def f16_pack_entries(entries):
+    """entries: [(w, wf, wd or None, M, C, taps)] -> ssad_f16_pack_entry[]"""
+    return _table(F16PackEntry, [(_ptr(w), _ptr(wf), _ptr(wd), M, Cc, taps, 0) for w, wf, wd, M, Cc, taps in entries])
+
+
+def pack_entries(entries):
+    """entries: [(w, cout, cin, pf or None, pd or None)] -> ssad_pack_entry[]"""
+    return _table(PackEntry, [(_ptr(w), cout, cin, _ptr(pf), _ptr(pd)) for w, cout, cin, pf, pd in entries])
+
+
+def grouped_pack_entries(entries):
+    """entries: [(w, pf or None, pd or None, C, group)] -> ssad_grouped_pack_entry[]"""
+    return _table(GroupedPackEntry, [(_ptr(w), _ptr(pf), _ptr(pd), Cc, group) for w, pf, pd, Cc, group in entries])
+
+
+def sgd_segments(segments):
+    """segments: [(offset, n, is_bias, row_len, s2 or None)] -> ssad_sgd_segment[]; row_len counts only beside a row
+    scale s2"""
+    return _table(SgdSegment, [(off, n, int(isb), row_len if s2 is not None else 0, _ptr(s2))
+                               for off, n, isb, row_len, s2 in segments])
+
+
+def f16_flags(relu=False, sigmoid=False, masked=False, out_nchw_f32=False):
+    """The flag word of the fp16 3x3 launchers."""
+    return ((CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0) | (CONV_MASK_AUX if masked else 0)
+            | (F16_OUT_NCHW_F32 if out_nchw_f32 else 0))
+
+
+# ---------------------------------------------------------------------------
 # conv 3x3
 # ---------------------------------------------------------------------------
 
@@ -873,8 +932,7 @@ def _pack_3x3(w, size, launch, what, *, table, pair, want_fwd=True, want_dgrad=T
         pf = torch.empty(size(Cout, Cin), dtype=torch.float32, device="cuda") if want_fwd else None
         pd = torch.empty(size(Cin, Cout), dtype=torch.float32, device="cuda") if want_dgrad else None
     if table:
-        tab = (PackEntry * 1)(PackEntry(w.data_ptr(), Cout, Cin, pf.data_ptr(), pd.data_ptr() if pd is not None else 0))
-        _check(launch(tab, 1, _stream()), what)
+        _check(launch(pack_entries([(w, Cout, Cin, pf, pd)]), 1, _stream()), what)
     else:
         _check(launch(_ptr(w), Cout, Cin, _ptr(pf), _ptr(pd), _stream()), what)
     return (pf, pd) if pair or pd is not None else pf
@@ -911,17 +969,11 @@ def conv_split_pack_filter(w, want_dgrad=False, out=None):
 
 
 def _conv_levels(xs, ys, auxs, packs=None, biases=None):
-    n = len(xs)
-    arr = (ConvLevel * n)()
-    for i in range(n):
-        N, _, H, W = xs[i].shape
-        arr[i] = ConvLevel(xs[i].data_ptr(),
-                           ys[i].data_ptr() if ys is not None and ys[i] is not None else 0,
-                           auxs[i].data_ptr() if auxs is not None and auxs[i] is not None else 0,
-                           N, H, W,
-                           packs[i].data_ptr() if packs is not None else 0,
-                           biases[i].data_ptr() if biases is not None and biases[i] is not None else 0)
-    return arr
+    """conv_levels() from columns: one list per field (or None = NULL in every level)."""
+    cols = [c if c is not None else [None] * len(xs) for c in (xs, ys, auxs, packs, biases)]
+    if min(len(c) for c in cols) < len(xs):         # the launch reads len(xs) levels of the table
+        raise KernelError("a level table needs one entry per level in every column")
+    return conv_levels(list(zip(*cols)))
 
 
 def _forward_3x3(launch, what, xs, packed, bias, Cout, *, relu, sigmoid, out, mask_by, flags=0, packs=None,
@@ -958,9 +1010,7 @@ def conv3x3_forward_split(xs, packed, bias, Cout, *, relu=False, sigmoid=False, 
 def conv3x3_split_items(shapes, Cout):
     """Work items (pixel tiles or pairs of half-tiles x 128-channel blocks) of a split-engine launch over levels of the
     given (N, H, W); follows SSAD_SPLIT_HALF_TILES like the launch itself.  Host arithmetic only."""
-    arr = (ConvLevel * len(shapes))()
-    for i, (N, H, W) in enumerate(shapes):
-        arr[i] = ConvLevel(0, 0, 0, N, H, W, 0, 0)
+    arr = _table(ConvLevel, [(None, None, None, N, H, W, None, None) for N, H, W in shapes])
     n = lib().ssad_conv3x3_split_items(arr, len(shapes), Cout)
     _check(min(n, 0), "conv3x3_split_items")
     return n
@@ -1091,11 +1141,15 @@ def conv3x3_forward_f16(xb, packed, bias, Cin, Cout, *, relu=False, sigmoid=Fals
         _f32c(bias, "bias")
     if mask_by is not None:
         assert mask_by.dtype == torch.float16 and mask_by.is_contiguous() and mask_by.shape == y.shape
-    flags = ((CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0)
-             | (CONV_MASK_AUX if mask_by is not None else 0) | (F16_OUT_NCHW_F32 if out_nchw_f32 else 0))
+    flags = f16_flags(relu, sigmoid, mask_by is not None, out_nchw_f32)
     _check(lib().ssad_conv3x3_forward_f16(_ptr(xb), _ptr(packed), _ptr(bias), _ptr(mask_by), N, Cin, H, W,
                                           Cout, flags, _ptr(y), _stream()), "conv3x3_forward_f16")
     return y
+
+
+def _f16_operands(xb, y, Cin, out_nchw_f32):
+    assert xb.dim() == 5 and xb.dtype == torch.float16 and xb.is_contiguous() and xb.shape[1] == (Cin + 7) // 8
+    assert y.is_contiguous() and y.dtype == (torch.float32 if out_nchw_f32 else torch.float16)
 
 
 def conv3x3_forward_f16_levels(xbs, packed, bias, Cin, Cout, outs, *, relu=False, sigmoid=False,
@@ -1103,19 +1157,15 @@ def conv3x3_forward_f16_levels(xbs, packed, bias, Cin, Cout, outs, *, relu=False
     """conv3x3_forward_f16 for every FPN level sharing the filter in one launch; `outs`
     (and `mask_bys`) are per-level lists."""
     n = len(xbs)
-    arr = (F16Level * n)()
-    for i, (xb, y) in enumerate(zip(xbs, outs)):
-        N, CB, H, W, _ = xb.shape
-        assert xb.dtype == torch.float16 and xb.is_contiguous() and CB == (Cin + 7) // 8
-        assert y.is_contiguous() and y.dtype == (torch.float32 if out_nchw_f32 else torch.float16)
-        arr[i].x, arr[i].y = xb.data_ptr(), y.data_ptr()
-        arr[i].aux = mask_bys[i].data_ptr() if mask_bys is not None else None
-        arr[i].N, arr[i].H, arr[i].W = N, H, W
+    masks = mask_bys if mask_bys is not None else [None] * n
+    assert len(outs) >= n and len(masks) >= n
+    for xb, y in zip(xbs, outs):
+        _f16_operands(xb, y, Cin, out_nchw_f32)
     if bias is not None:
         _f32c(bias, "bias")
-    flags = ((CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0)
-             | (CONV_MASK_AUX if mask_bys is not None else 0) | (F16_OUT_NCHW_F32 if out_nchw_f32 else 0))
-    _check(lib().ssad_conv3x3_forward_f16_levels(arr, n, _ptr(packed), _ptr(bias), Cin, Cout, flags,
+    arr = f16_levels([(xb, y, m, None, None) for xb, y, m in zip(xbs, outs, masks)])
+    _check(lib().ssad_conv3x3_forward_f16_levels(arr, n, _ptr(packed), _ptr(bias), Cin, Cout,
+                                                 f16_flags(relu, sigmoid, mask_bys is not None, out_nchw_f32),
                                                  _stream()), "conv3x3_forward_f16_levels")
     return outs
 
@@ -1124,27 +1174,18 @@ def conv3x3_forward_f16_multi(problems, Cin, Cout, *, relu=False, sigmoid=False,
     """Independent fp16 convolutions of equal (Cin, Cout) in ONE launch.  problems: dicts
     {xs, packed, bias, out, mask_by(optional, all or none)} -- e.g. the cls- and bbox-tower layer
     of the same depth for teacher and student."""
-    n = sum(len(p["xs"]) for p in problems)
-    arr = (F16Level * n)()
     masked = [p.get("mask_by") is not None for p in problems]
     assert all(masked) or not any(masked)
-    i = 0
+    rows = []
     for p in problems:
         if p.get("bias") is not None:
             _f32c(p["bias"], "bias")
+        assert len(p["out"]) >= len(p["xs"]) and p["packed"] is not None
         for l, (xb, y) in enumerate(zip(p["xs"], p["out"])):
-            N, CB, H, W, _ = xb.shape
-            assert xb.dtype == torch.float16 and xb.is_contiguous() and CB == (Cin + 7) // 8
-            assert y.is_contiguous() and y.dtype == (torch.float32 if out_nchw_f32 else torch.float16)
-            arr[i].x, arr[i].y = xb.data_ptr(), y.data_ptr()
-            arr[i].aux = p["mask_by"][l].data_ptr() if masked[0] else None
-            arr[i].N, arr[i].H, arr[i].W = N, H, W
-            arr[i].packed = p["packed"].data_ptr()
-            arr[i].bias = p["bias"].data_ptr() if p.get("bias") is not None else None
-            i += 1
-    flags = ((CONV_RELU if relu else 0) | (CONV_SIGMOID if sigmoid else 0)
-             | (CONV_MASK_AUX if masked[0] else 0) | (F16_OUT_NCHW_F32 if out_nchw_f32 else 0))
-    _check(lib().ssad_conv3x3_forward_f16_levels(arr, n, None, None, Cin, Cout, flags, _stream()),
+            _f16_operands(xb, y, Cin, out_nchw_f32)
+            rows.append((xb, y, p["mask_by"][l] if masked[0] else None, p["packed"], p.get("bias")))
+    _check(lib().ssad_conv3x3_forward_f16_levels(f16_levels(rows), len(rows), None, None, Cin, Cout,
+                                                 f16_flags(relu, sigmoid, masked[0], out_nchw_f32), _stream()),
            "conv3x3_forward_f16_multi")
 
 
@@ -1157,13 +1198,13 @@ def conv3x3_wgrad_f16(xbs, dybs, Cin, Cout, *, scale=1.0, dW=None, db=None, bias
         db = torch.empty((Cout,), dtype=torch.float32, device="cuda")
     L = lib()
     n = len(xbs)
-    arr = (F16WgradLevel * n)()
-    for i, (xb, dyb) in enumerate(zip(xbs, dybs)):
+    assert len(dybs) >= n
+    for xb, dyb in zip(xbs, dybs):
         N, CB, H, W, _ = xb.shape
         assert xb.dtype == torch.float16 and dyb.dtype == torch.float16
         assert xb.is_contiguous() and dyb.is_contiguous()
         assert CB == (Cin + 7) // 8 and dyb.shape == (N, (Cout + 7) // 8, H, W, 8)
-        arr[i].x, arr[i].dy, arr[i].N, arr[i].H, arr[i].W = xb.data_ptr(), dyb.data_ptr(), N, H, W
+    arr = f16_wgrad_levels(xbs, dybs)
     nbytes = L.ssad_conv3x3_wgrad_f16_levels_workspace_bytes(arr, n, Cin, Cout)
     ws = _workspace(nbytes, "wgrad_f16")
     _check(L.ssad_conv3x3_wgrad_f16_levels(arr, n, Cin, Cout, 0, float(scale), _ptr(dW), _ptr(db), _ptr(ws),
@@ -1459,7 +1500,6 @@ def grouped_conv3x3_pack_filters(entries):
     is checked before anything is written."""
     if not entries:
         raise KernelError("grouped_conv3x3_pack_filters: an empty table")
-    tab = (GroupedPackEntry * len(entries))()
     for k, (w, group, pf, pd) in enumerate(entries):
         _f32c(w, "w")
         Cc = w.shape[0]
@@ -1475,8 +1515,7 @@ def grouped_conv3x3_pack_filters(entries):
                 if t.numel() < n:
                     raise KernelError("grouped_conv3x3_pack_filters: entry %d: %s holds %d floats, the pack has %d"
                                       % (k, name, t.numel(), n))
-        tab[k] = GroupedPackEntry(w.data_ptr(), pf.data_ptr() if pf is not None else None,
-                                  pd.data_ptr() if pd is not None else None, Cc, group)
+    tab = grouped_pack_entries([(w, pf, pd, w.shape[0], group) for w, group, pf, pd in entries])
     _check(lib().ssad_grouped_conv3x3_pack_filters(tab, len(entries), _stream()), "grouped_conv3x3_pack_filters")
 
 

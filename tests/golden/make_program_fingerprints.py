@@ -259,6 +259,14 @@ def configurations():
     out.append(("f16_r50_own_io_train", {}, backbone(cls=NativeResNetFPNF16, train=True)))
     out.append(("f16_r50_own_io_no_overlap_wgrad_train", {},
                 backbone(cls=NativeResNetFPNF16, train=True, overlap_wgrad=False)))
+    # the fp16 subnets without a teacher and on blocked input, the frozen fp16 teachers (the second one has the
+    # GROUPED_F16_CG64 records) and a trained ResNeXt, the one program with a GROUPED_PACKS table
+    out.append(("heads_f16_plain", {}, heads(cls=DistillHeadsF16, distill=False)))
+    out.append(("heads_f16_blocked_one_level", {}, heads(cls=DistillHeadsF16, shapes=[(5, 7)], blocked_io=True)))
+    out.append(("f16_r101_frozen", {}, backbone("r101", cls=NativeResNetFPNF16, train=False)))
+    out.append(("f16_x101_32x8d_wide_frozen", {},
+                backbone("x101-32x8d", cls=NativeResNetFPNF16, train=False, wide_groups=True)))
+    out.append(("x101_64x4d_grouped_grad_train", {}, backbone("x101-64x4d", train=True, grouped_grad=True)))
     return out
 
 

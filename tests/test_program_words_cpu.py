@@ -10,7 +10,8 @@ import torch
 import ssad_amd  # noqa: F401
 from ssad_amd import backbone_pipeline as BP, kernels as K, program as PR
 from ssad_amd.backbone_f16 import NativeResNetFPNF16
-from ssad_amd.engines import AmaxTable, conv_table
+from ssad_amd.engines import AmaxTable
+from ssad_amd.kernels import conv_levels as conv_table
 from ssad_amd.head_pipeline import DistillHeads, DistillHeadsF16
 from ssad_amd.modeling.retinanet_heads import HeadConfig
 
