@@ -25,8 +25,12 @@ Kernels:
     projection); P6 / P7 (3x3 / stride 2) run at their own size: implicit GEMM with split-K forward,
     flattened-batch GEMMs + gather-form col2im for the gradients (csrc/kernels/conv_strided.hip;
     SSAD_STRIDED_3X3=winograd: the stride-1 Winograd layer + subsampling of rounds 1-2, 4x the flops);
-  * the 7x7 / stride 2 stem: batched im2col + the same GEMM, then bias + ReLU + 3x3/2 max pool
+  * the 7x7 / stride 2 stem: an implicit GEMM (K = 147, no column buffer), then bias + ReLU + 3x3/2 max pool
     in one pass (ssad_max_pool3x3s2_bias_relu).
+
+_emit_forward / _emit_backward are the one statement of the network for both precisions: what is computed in which
+order.  How an operation is emitted is a method ("the operations of the walk"); backbone_f16.NativeResNetFPNF16
+overrides those and defines no walk of its own.
 
 All activations, gradients and packed filters are allocated once; the step is
 Program.run() calls (ssad_program_run) -- a few segments when data parallel, so that a stage's
@@ -367,6 +371,10 @@ class NativeResNetFPN(object):
         self._bufs.append(u)
         return u
 
+    def _act(self, N, Cc, H, W):
+        """An activation or gradient buffer of the network in this precision's layout: here NCHW fp32."""
+        return self._t(N, Cc, H, W)
+
     # |max| words of the split-operand engines (engines.AmaxTable): one word per tensor.  The producers of the forward
     # pass fold (every activation is written exactly once there) and, in the backward pass, those of the three gradients
     # inside a bottleneck block (fold=True at their call sites); the other gradient buffers are also summed in place by
@@ -460,6 +468,7 @@ class NativeResNetFPN(object):
               work=2.0 * 9 * Cc * layer.wcin * N * dy.shape[2] * dy.shape[3])
 
     def _wgrad1(self, P, x, dy, layer):
+        """Filter gradient of a pointwise layer, and the bias gradient of one that trains its bias (the laterals)."""
         N, Cc = x.shape[0], x.shape[1]
         pix = x.shape[2] * x.shape[3]
         # SSAD_SPLIT_CONV bit 256: the compute-bound pointwise filter gradients (C, M >= 256, the launch's pixels as for
@@ -477,6 +486,8 @@ class NativeResNetFPN(object):
         stream, ws = self._aux(P)
         P.add(PR.CONV1X1_WGRAD, 72 if split else 52, i=(N, Cc, pix, layer.cout, 0, 1 if split else 0), l=(nb,),
               p=(x, dy, layer.gw, ws.need(nb), xa, da), work=2.0 * N * pix * Cc * layer.cout, keep=[x, dy], stream=stream)
+        if layer.gb is not None:
+            self._bias_grad(P, dy, layer)
 
     def _bias_grad(self, P, dz, layer, rowsum=None):
         """db[c] = sum over n, pixels of dz; from the [N][C] plane sums when a ReluGradient pass
@@ -637,15 +648,7 @@ class NativeResNetFPN(object):
         self._packed_frozen = False
         P.mark("forward")
         P.add(PR.FILL, 51, p=(self.amax,), f=(0.0,), l=(self.AMAX_WORDS,), work=4.0 * self.AMAX_WORDS)
-        self._fwd = True
-        self._emit_forward(P)
-        self._fwd = False
-        P.mark("backward")
-        if self.train:
-            self._emit_backward(P)
-            P.mark("sgd")
-            self._emit_sgd(P)
-        P.mark("end")
+        self._emit_passes(P)
         for train, entries, prog in ((True, self._gpack_train, P), (False, self._gpack_frozen, prep)):
             for k, (a, lda, Kc, M, dst) in enumerate(entries):
                 gtab[train][k] = K.GemmPackEntry(a.data_ptr(), dst.data_ptr(), lda, Kc, M)
@@ -656,20 +659,100 @@ class NativeResNetFPN(object):
         self._bind_workspaces()
         P.build()
 
+    def _emit_passes(self, P):
+        """The walk into P (behind the "forward" mark): forward, and for a trained network backward and the update."""
+        self._fwd = True              # (every activation is written once there: its producer folds its |max| word)
+        self._emit_forward(P)
+        self._fwd = False
+        P.mark("backward")
+        if self.train:
+            self._emit_backward(P)
+            P.mark("sgd")
+            self._emit_sgd(P)
+        P.mark("end")
+
+    # -- the operations of the walk, as this precision emits them (backbone_f16 overrides these) -------------------
+    # An operation that sums or accumulates returns the tensor that holds the result -- here its in-place operand, in
+    # fp16 a fresh buffer -- and the walk goes on with what it was handed.  Cc: the channels of the tensors (a blocked
+    # fp16 tensor's shape does not tell).
+    def _stem_pool(self, P, st, z, y):
+        """y = 3x3 / 2 max pool of relu(z + bias)."""
+        N, Cc, oh, ow = z.shape
+        self._ew(P, PR.STEM_POOL, i=(N, Cc, oh, ow, 1), p=(z, st.b, y), nbytes=4.0 * 1.25 * z.numel())
+
+    def _subsample(self, P, x, y, Cc, stride):
+        """y = every stride-th position of x."""
+        self._ew(P, PR.SUBSAMPLE, i=(self.N, Cc, x.shape[2], x.shape[3], stride), p=(x, y), nbytes=8.0 * y.numel())
+
+    def _subsample_grad(self, P, dy, dx, Cc, stride, acc=False):
+        """dx = dy at every stride-th position, zero elsewhere; acc: added to what dx holds."""
+        self._ew(P, PR.SUBSAMPLE_GRAD, i=(self.N, Cc, dx.shape[2], dx.shape[3], stride, int(acc)), p=(dy, dx),
+                 nbytes=(12.0 if acc else 4.0) * dx.numel())
+
+    def _relu(self, P, x, y, Cc):
+        self._ew(P, PR.RELU, p=(x, y), l=(x.numel(),), nbytes=8.0 * x.numel())
+
+    def _relu_grad(self, P, y, dy, dz, Cc):
+        """dz = ReluGradient(y, dy)."""
+        self._ew(P, PR.RELU_GRAD, p=(y, dy, dz), l=(y.numel(),), nbytes=12.0 * y.numel())
+
+    def _sum2(self, P, a, b, Cc):
+        """a + b -> the tensor that holds the sum (a, in place)."""
+        ptrs = (C.c_void_p * 2)(a.data_ptr(), b.data_ptr())
+        P.add(PR.SUM_N, 51, i=(2,), l=(a.numel(),), p=(ptrs, a), work=12.0 * a.numel(), keep=[a, b])
+        return a
+
+    def _topdown_grad(self, P, fine, coarse):
+        """coarse + the 2 x 2 sums of fine (fine = lateral + up(coarse) in the forward pass) -> the tensor that holds it."""
+        up = self._like(coarse)
+        self._ew(P, PR.UPSAMPLE_GRAD, i=(self.N, self.D, coarse.shape[2], coarse.shape[3], 2), p=(fine, up),
+                 nbytes=5.0 * fine.numel())
+        return self._sum2(P, coarse, up, self.D)
+
+    def _pointwise(self, P, l, x, y, res=None, relu=False):
+        """y = W x + bias (+ res), through ReLU when asked."""
+        self._gemm(P, l.wt, l.wt.shape[1], x, y, l.cin, l.cout, bias=l.b, res=res, relu=relu)
+
+    def _lateral(self, P, l, c, t, top=None):
+        """t = W c + bias (+ top, upsampled 2 x nearest: in place behind the GEMM)."""
+        self._gemm(P, l.wt, l.wt.shape[1], c, t, l.cin, l.cout, bias=l.b, final=top is None)
+        if top is not None:
+            self._ew(P, PR.UPSAMPLE, i=(self.N, l.cout, top.shape[2], top.shape[3], 2), p=(top, t, t), nbytes=9.0 * t.numel())
+
+    def _pointwise_grad(self, P, l, dy, like=None, mask=None, res=None, into=None, fold=False):
+        """W^T dy (+ res), through the ReluGradient mask when given, in a new buffer shaped like `like` -- or, into=:
+        added to the gradient that tensor already holds.  -> the tensor that holds the result (into itself)."""
+        dx = self._like(like) if into is None else into
+        self._gemm(P, l.w.view(l.cout, l.cin), l.cin, dy, dx, l.cout, l.cin, res=res, mask=mask, acc=into is not None,
+                   fold=fold)
+        return dx
+
+    def _grouped3(self, P, l, x, y):
+        """y = relu(grouped 3x3 of x + bias) at the layer's stride."""
+        P.add(PR.GROUPED_CONV3X3, 56, i=(self.N, l.cin, x.shape[2], x.shape[3], l.group, l.stride, 1),
+              p=(x, l.pf, l.b, y), work=2.0 * 9 * l.cin * l.wcin * self.N * y.shape[2] * y.shape[3])
+
+    def _fpn_level(self, k, h, w):
+        """The buffer of FPN level k (0: P3 ... 4: P7)."""
+        return self._act(self.N, self.D, h, w)
+
+    def _fpn_grads(self, P):
+        """The gradients w.r.t. the FPN levels (subnet gradients, summed): written by the caller."""
+        return [self._like(p) for p in self.fpn]
+
     # -- forward ----------------------------------------------------------------------------------------
     def _emit_forward(self, P):
-        L, N = self._layers, self.N
+        """The network, once for both precisions: what is computed in which order.  How an operation is emitted is the
+        methods' above."""
+        L, N, D = self._layers, self.N, self.D
         H, W = self.hw
         self.image = self._t(N, 3, H, W)
-        # stem: im2col + GEMM (K = 147), then bias + ReLU + 3x3/2 max pool in one pass.  The column
-        # buffer of the whole batch is ~1.35 GB at 640x896 x 16: processed in image groups below 2 GiB.
+        # stem (fp32 in either precision: Cin = 3): 7x7 / 2 as an implicit GEMM (K = 147 gathered by the DMA: no column
+        # buffer), then bias + ReLU + 3x3 / 2 max pool in one pass.  Image groups keep every buffer offset below 2 GiB.
         st = L["stem.0"]
         oh, ow = H // 2, W // 2
         kk = 3 * 49
         self.stem_z = self._t(N, st.cout, oh, ow)
-        # stem: 7x7/2 as an implicit GEMM (K = 147 gathered by the DMA: no column buffer -- it was
-        # 1.35 GB per 16 images), then bias + ReLU + 3x3/2 max pool in one pass.  Image groups keep
-        # every buffer offset below 2 GiB.
         grp = max(1, min(N, int((1 << 31) - 1) // (st.cout * oh * ow * 4)))
         for n0 in range(0, N, grp):
             n1 = min(N, n0 + grp)
@@ -677,9 +760,8 @@ class NativeResNetFPN(object):
             d.P = oh * ow
             P.add(PR.CONV_IMPLICIT, 53, i=(3, H, W, 7, 2, 3), p=(d,), work=2.0 * (n1 - n0) * oh * ow * kk * st.cout,
                   keep=[st.wt, self.image, self.stem_z])
-        c1 = self._t(N, st.cout, oh // 2, ow // 2)
-        self._ew(P, PR.STEM_POOL, i=(N, st.cout, oh, ow, 1), p=(self.stem_z, st.b, c1), nbytes=4.0 * 1.25 * self.stem_z.numel())
-        x = c1
+        x = self._act(N, st.cout, oh // 2, ow // 2)
+        self._stem_pool(P, st, self.stem_z, x)
         self.saved = {}
         stage_out = {}
         for (stage, j, cin, cmid, cout, stride, proj, tr) in self.blocks:
@@ -687,104 +769,77 @@ class NativeResNetFPN(object):
             l1, l2, l3 = L[pre + ".c1"], L[pre + ".c2"], L[pre + ".c3"]
             h, w = x.shape[2] // stride, x.shape[3] // stride
             xs = x
-            if stride != 1:
-                xs = self._t(N, cin, h, w)
-                self._ew(P, PR.SUBSAMPLE, i=(N, cin, x.shape[2], x.shape[3], stride), p=(x, xs), nbytes=8.0 * xs.numel())
+            if stride != 1:                                   # shared by c1 (ResNet) and the projection
+                xs = self._act(N, cin, h, w)
+                self._subsample(P, x, xs, cin, stride)
             a = xs if l1.stride == stride else x              # ResNeXt strides on the 3x3: c1 sees the full map
-            y1 = self._t(N, cmid, a.shape[2], a.shape[3])
-            y2, y = self._t(N, cmid, h, w), self._t(N, cout, h, w)
-            self._gemm(P, l1.wt, l1.wt.shape[1], a, y1, cin, cmid, bias=l1.b, relu=True)
+            y1 = self._act(N, cmid, a.shape[2], a.shape[3])
+            y2, y = self._act(N, cmid, h, w), self._act(N, cout, h, w)
+            self._pointwise(P, l1, a, y1, relu=True)
             if l2.group > 1:
-                P.add(PR.GROUPED_CONV3X3, 56, i=(N, cmid, y1.shape[2], y1.shape[3], l2.group, l2.stride, 1),
-                      p=(y1, l2.pf, l2.b, y2), work=2.0 * 9 * cmid * l2.wcin * y2.shape[0] * h * w)
+                self._grouped3(P, l2, y1, y2)
             else:
                 self._conv3(P, [(y1, y2, None, l2.pf, l2.b)], cmid, cmid, K.CONV_RELU, l2.engine)
             sc = xs
             if proj:
-                lp = L[pre + ".proj"]
-                sc = self._t(N, cout, h, w)
-                self._gemm(P, lp.wt, lp.wt.shape[1], xs, sc, cin, cout, bias=lp.b)
-            self._gemm(P, l3.wt, l3.wt.shape[1], y2, y, cmid, cout, bias=l3.b, res=sc, relu=True)
+                sc = self._act(N, cout, h, w)
+                self._pointwise(P, L[pre + ".proj"], xs, sc)
+            self._pointwise(P, l3, y2, y, res=sc, relu=True)
             self.saved[pre] = dict(x=x, xs=xs, y1=y1, y2=y2, y=y, c1_in=a)
             x = y
             stage_out[stage] = y
-        c3, c4, c5 = stage_out[3], stage_out[4], stage_out[5]
-        self.c345 = (c3, c4, c5)
-        D = self.D
-        # FPN: laterals (GEMM + bias), top-down nearest upsampling + Sum in place
-        t5 = self._t(N, D, c5.shape[2], c5.shape[3])
-        t4 = self._t(N, D, c4.shape[2], c4.shape[3])
-        t3 = self._t(N, D, c3.shape[2], c3.shape[3])
-        for t, c, name in ((t5, c5, "lat.0"), (t4, c4, "lat.1"), (t3, c3, "lat.2")):
-            l = L[name]
-            self._gemm(P, l.wt, l.wt.shape[1], c, t, l.cin, D, bias=l.b, final=t is t5)
-            if t is not t5:
-                src = t5 if t is t4 else t4
-                self._ew(P, PR.UPSAMPLE, i=(N, D, src.shape[2], src.shape[3], 2), p=(src, t, t), nbytes=9.0 * t.numel())
-        p5, p4, p3 = (self._like(t) for t in (t5, t4, t3))
+        c3, c4, c5 = self.c345 = (stage_out[3], stage_out[4], stage_out[5])
+        # FPN: laterals, each but the first summed with the level above (nearest upsampling); 3x3 output convolutions
+        t5, t4, t3 = (self._act(N, D, c.shape[2], c.shape[3]) for c in (c5, c4, c3))
+        self._lateral(P, L["lat.0"], c5, t5)
+        self._lateral(P, L["lat.1"], c4, t4, top=t5)
+        self._lateral(P, L["lat.2"], c3, t3, top=t4)
+        p5, p4, p3 = (self._fpn_level(k, t.shape[2], t.shape[3]) for k, t in ((2, t5), (1, t4), (0, t3)))
         self._conv3(P, [(t, p, None, L[name].pf, L[name].b)                # three filters, one launch
                         for t, p, name in ((t5, p5, "out.0"), (t4, p4, "out.1"), (t3, p3, "out.2"))], D, D, 0,
                    same_engine(L[name].engine for name in ("out.0", "out.1", "out.2")))
-        l6, l7 = L["p6"], L["p7"]
-        if self._strided_own:
-            # P6 / P7 (3x3, stride 2) at their own size
-            p6 = self._t(N, D, (c5.shape[2] - 1) // 2 + 1, (c5.shape[3] - 1) // 2 + 1)
-            self._conv_s2(P, c5, p6, l6)
-            r6 = self._like(p6)
-            self._ew(P, PR.RELU, p=(p6, r6), l=(p6.numel(),), nbytes=8.0 * p6.numel())
-            p7 = self._t(N, D, (p6.shape[2] - 1) // 2 + 1, (p6.shape[3] - 1) // 2 + 1)
-            self._conv_s2(P, r6, p7, l7)
-            p6f = p7f = None
-        else:
-            # SSAD_STRIDED_3X3=winograd: stride-1 convolution, then the even positions
-            p6f = self._t(N, D, c5.shape[2], c5.shape[3])
-            self._conv3(P, [(c5, p6f, None, l6.pf, l6.b)], D, l6.cin, 0, l6.engine)
-            p6 = self._t(N, D, c5.shape[2] // 2, c5.shape[3] // 2)
-            self._ew(P, PR.SUBSAMPLE, i=(N, D, c5.shape[2], c5.shape[3], 2), p=(p6f, p6), nbytes=8.0 * p6.numel())
-            r6 = self._like(p6)
-            self._ew(P, PR.RELU, p=(p6, r6), l=(p6.numel(),), nbytes=8.0 * p6.numel())
-            p7f = self._like(p6)
-            self._conv3(P, [(r6, p7f, None, l7.pf, l7.b)], D, D, 0, l7.engine)
-            p7 = self._t(N, D, (p6.shape[2] + 1) // 2, (p6.shape[3] + 1) // 2)
-            self._ew(P, PR.SUBSAMPLE, i=(N, D, p6.shape[2], p6.shape[3], 2), p=(p7f, p7), nbytes=8.0 * p7.numel())
+        p6, p7, r6, p6f, p7f = (self._emit_p6p7_own if self._strided_own else self._emit_p6p7)(P, c5)
         self.fpn = [p3, p4, p5, p6, p7]                   # finest first (synth.LEVEL_SHAPES_*)
         self._fpn_saved = dict(t3=t3, t4=t4, t5=t5, r6=r6, p6f=p6f, p7f=p7f)
+
+    def _emit_p6p7(self, P, c5):
+        """P6 = conv3x3 / 2 (c5), P7 = conv3x3 / 2 (relu(P6)) as the stride-1 layer + the even positions (fp32:
+        SSAD_STRIDED_3X3=winograd).  -> p6, p7, relu(p6), the two full-size maps"""
+        N, D = self.N, self.D
+        l6, l7 = self._layers["p6"], self._layers["p7"]
+        p6f = self._act(N, D, c5.shape[2], c5.shape[3])
+        self._conv3(P, [(c5, p6f, None, l6.pf, l6.b)], D, l6.cin, 0, l6.engine)
+        p6 = self._fpn_level(3, c5.shape[2] // 2, c5.shape[3] // 2)
+        self._subsample(P, p6f, p6, D, 2)
+        r6 = self._like(p6)
+        self._relu(P, p6, r6, D)
+        p7f = self._like(p6)
+        self._conv3(P, [(r6, p7f, None, l7.pf, l7.b)], D, D, 0, l7.engine)
+        p7 = self._fpn_level(4, (p6.shape[2] + 1) // 2, (p6.shape[3] + 1) // 2)
+        self._subsample(P, p7f, p7, D, 2)
+        return p6, p7, r6, p6f, p7f
+
+    def _emit_p6p7_own(self, P, c5):
+        """The same at the layers' own size (conv_strided.hip; fp32 only, the default).  -> as _emit_p6p7"""
+        N, D = self.N, self.D
+        p6 = self._t(N, D, (c5.shape[2] - 1) // 2 + 1, (c5.shape[3] - 1) // 2 + 1)
+        self._conv_s2(P, c5, p6, self._layers["p6"])
+        r6 = self._like(p6)
+        self._relu(P, p6, r6, D)
+        p7 = self._t(N, D, (p6.shape[2] - 1) // 2 + 1, (p6.shape[3] - 1) // 2 + 1)
+        self._conv_s2(P, r6, p7, self._layers["p7"])
+        return p6, p7, r6, None, None
 
     # -- backward ------------------------------------------------------------------------------------------
     def _emit_backward(self, P):
         L, N, D = self._layers, self.N, self.D
         c3, c4, c5 = self.c345
         S = self._fpn_saved
-        t3, t4, t5, r6 = S["t3"], S["t4"], S["t5"], S["r6"]
-        # gradient w.r.t. every FPN level, written by the caller (subnet gradients, summed)
-        self.d_fpn = [self._like(p) for p in self.fpn]
+        t3, t4, t5 = S["t3"], S["t4"], S["t5"]
+        self.d_fpn = self._fpn_grads(P)
         d3, d4, d5, d6, d7 = self.d_fpn
-        l6, l7 = L["p6"], L["p7"]
         dc5 = self._like(c5)
-        if self._strided_own:
-            # P7 = conv_s2(relu(p6)): filter gradient, then the data gradient masked by p6 > 0, added to P6's own
-            self._wgrad_s2(P, r6, d7, l7)
-            dr6 = self._like(r6)
-            self._dgrad_s2(P, l7, d7, dr6, mask=r6)
-            ptrs = (C.c_void_p * 2)(d6.data_ptr(), dr6.data_ptr())
-            P.add(PR.SUM_N, 51, i=(2,), l=(d6.numel(),), p=(ptrs, d6), work=12.0 * d6.numel(), keep=[d6, dr6])
-            # P6 = conv_s2(c5)
-            self._wgrad_s2(P, c5, d6, l6)
-            self._dgrad_s2(P, l6, d6, dc5)
-        else:
-            # P7 = sub(conv(relu(p6)))
-            d7f = self._like(S["p7f"])
-            self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, D, d7f.shape[2], d7f.shape[3], 2, 0), p=(d7, d7f), nbytes=4.0 * d7f.numel())
-            self._wgrad3(P, r6, d7f, l7)
-            dr6 = self._like(r6)
-            self._conv3(P, [(d7f, dr6, r6, l7.pd, None)], D, D, K.CONV_MASK_AUX, l7.engine)   # masked by p6 > 0
-            ptrs = (C.c_void_p * 2)(d6.data_ptr(), dr6.data_ptr())
-            P.add(PR.SUM_N, 51, i=(2,), l=(d6.numel(),), p=(ptrs, d6), work=12.0 * d6.numel(), keep=[d6, dr6])
-            # P6 = sub(conv(c5))
-            d6f = self._like(S["p6f"])
-            self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, D, d6f.shape[2], d6f.shape[3], 2, 0), p=(d6, d6f), nbytes=4.0 * d6f.numel())
-            self._wgrad3(P, c5, d6f, l6)
-            self._conv3(P, [(d6f, dc5, None, l6.pd, None)], l6.cin, D, 0, l6.engine)
+        (self._emit_p6p7_own_grad if self._strided_own else self._emit_p6p7_grad)(P, c5, d6, d7, dc5)
         # output convs: filter gradients and the three data gradients in one launch
         dt5, dt4, dt3 = self._like(t5), self._like(t4), self._like(t3)
         if L["out.0"].engine == Engine.SPLIT:
@@ -796,23 +851,15 @@ class NativeResNetFPN(object):
                         for d, dt, name in ((d5, dt5, "out.0"), (d4, dt4, "out.1"), (d3, dt3, "out.2"))], D, D, 0,
                    same_engine(L[name].engine for name in ("out.0", "out.1", "out.2")))
         # top-down path: t3 = lat2(c3) + up(t4), t4 = lat1(c4) + up(t5)
-        up4, up5 = self._like(t4), self._like(t5)
-        self._ew(P, PR.UPSAMPLE_GRAD, i=(N, D, t4.shape[2], t4.shape[3], 2), p=(dt3, up4), nbytes=5.0 * dt3.numel())
-        ptrs4 = (C.c_void_p * 2)(dt4.data_ptr(), up4.data_ptr())
-        P.add(PR.SUM_N, 51, i=(2,), l=(dt4.numel(),), p=(ptrs4, dt4), work=12.0 * dt4.numel(), keep=[dt4, up4])
-        self._ew(P, PR.UPSAMPLE_GRAD, i=(N, D, t5.shape[2], t5.shape[3], 2), p=(dt4, up5), nbytes=5.0 * dt4.numel())
-        ptrs5 = (C.c_void_p * 2)(dt5.data_ptr(), up5.data_ptr())
-        P.add(PR.SUM_N, 51, i=(2,), l=(dt5.numel(),), p=(ptrs5, dt5), work=12.0 * dt5.numel(), keep=[dt5, up5])
-        # laterals: filter / bias gradients; data gradients meet the stage outputs' other consumers
-        dc4, dc3 = self._like(c4), self._like(c3)
-        for c, dt, dc, name, acc in ((c5, dt5, dc5, "lat.0", True), (c4, dt4, dc4, "lat.1", False),
-                                     (c3, dt3, dc3, "lat.2", False)):
-            l = L[name]
-            self._wgrad1(P, c, dt, l)
-            self._bias_grad(P, dt, l)
-            self._gemm(P, l.w.view(l.cout, l.cin), l.cin, dt, dc, l.cout, l.cin, acc=acc)
+        dt4 = self._topdown_grad(P, dt3, dt4)
+        dt5 = self._topdown_grad(P, dt4, dt5)
+        # laterals: filter / bias gradients; data gradients meet the stage outputs' other consumers (c5's: P6)
+        grads_into = {}
+        for stage, c, dt, name, into in ((5, c5, dt5, "lat.0", dc5), (4, c4, dt4, "lat.1", None),
+                                         (3, c3, dt3, "lat.2", None)):
+            self._wgrad1(P, c, dt, L[name])
+            grads_into[stage] = self._pointwise_grad(P, L[name], dt, like=c, into=into)
         P.mark("bwd_fpn_done")
-        grads_into = {5: dc5, 4: dc4, 3: dc3}
         dy = None
         dy_is_dz = False          # dy already went through this block's ReluGradient (previous GEMM's epilogue)
         for (stage, j, cin, cmid, cout, stride, proj, tr) in reversed(self.blocks):
@@ -822,13 +869,11 @@ class NativeResNetFPN(object):
             l1, l2, l3 = L[pre + ".c1"], L[pre + ".c2"], L[pre + ".c3"]
             sv = self.saved[pre]
             x, xs, y1, y2, y = sv["x"], sv["xs"], sv["y1"], sv["y2"], sv["y"]
-            last_of_stage = j == ARCHS[self.arch][stage - 2] - 1
-            if last_of_stage:
+            if j == ARCHS[self.arch][stage - 2] - 1:
                 # the stage's output feeds the lateral (already in grads_into) and, for res3 / res4,
                 # the next stage's first block, whose input gradient was accumulated onto it
                 dy = grads_into[stage]
                 dy_is_dz = False
-            h, w = y.shape[2], y.shape[3]
             if dy_is_dz:
                 # the block below (later in the forward order) produced dy with this block's
                 # ReluGradient mask already applied in its GEMM epilogue: no elementwise pass
@@ -837,13 +882,13 @@ class NativeResNetFPN(object):
                 # dz = ReluGradient(y, dy).  (No bias gradients in the body: the folded AffineChannel
                 # biases are frozen values, affine_channel_op.cc.)
                 dz = self._like(y)
-                self._ew(P, PR.RELU_GRAD, p=(y, dy, dz), l=(y.numel(),), nbytes=12.0 * y.numel())
+                self._relu_grad(P, y, dy, dz, cout)
             self._wgrad1(P, y2, dz, l3)
-            dz2 = self._like(y2)
-            self._gemm(P, l3.w.view(cout, cmid), cmid, dz, dz2, cout, cmid, mask=y2, fold=True)
+            dz2 = self._pointwise_grad(P, l3, dz, like=y2, mask=y2, fold=True)
             dz1 = self._like(y1)
             if l2.group > 1:
-                # ResNeXt: y1 (and so dz1) is at c1's input size, dz2 at the block's output size (stride on the 3x3)
+                # ResNeXt (fp32 only): y1 (and so dz1) is at c1's input size, dz2 at the block's output size (stride on
+                # the 3x3)
                 self._wgrad_grouped(P, y1, dz2, l2)
                 self._dgrad_grouped(P, dz2, dz1, y1, l2)
             else:
@@ -852,43 +897,65 @@ class NativeResNetFPN(object):
             sv["dz2"], sv["dz1"] = dz2, dz1
             c1_in = sv["c1_in"]                                            # xs; the full map x in a ResNeXt
             self._wgrad1(P, c1_in, dz1, l1)
-            first_trainable = (stage == 3 and j == 0)
             if proj:
                 lp = L[pre + ".proj"]
                 self._wgrad1(P, xs, dz, lp)
-                if not first_trainable and c1_in is not xs:
-                    # ResNeXt, stride 2: the two parts of the input gradient live at different sizes.  W1^T dz1 is
-                    # x-shaped: straight onto the previous stage's output gradient (which already holds the lateral's
-                    # part); Wp^T dz is xs-shaped: scattered onto it afterwards.  Always in this order: same bits.
-                    # (In place, unlike _aux's rule for gradients that meet: no auxiliary-stream launch reads tgt -- the
-                    # lateral's filter gradient reads the stage output and dt, not this buffer -- and its first reader,
-                    # the previous stage's ReluGradient, is emitted on the main stream behind both writes.)
-                    tgt = grads_into[stage - 1]
-                    self._gemm(P, l1.w.view(cmid, cin), cin, dz1, tgt, cmid, cin, acc=True)
-                    dxs = self._like(xs)
-                    self._gemm(P, lp.w.view(cout, cin), cin, dz, dxs, cout, cin)
-                    self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, cin, x.shape[2], x.shape[3], stride, 1), p=(dxs, tgt),
-                             nbytes=12.0 * tgt.numel())
-                elif not first_trainable:
-                    dxs = self._like(xs)
-                    self._gemm(P, l1.w.view(cmid, cin), cin, dz1, dxs, cmid, cin)
-                    self._gemm(P, lp.w.view(cout, cin), cin, dz, dxs, cout, cin, acc=True)
-                    # into the previous stage's output gradient (which already holds the lateral's part)
-                    tgt = grads_into[stage - 1]
-                    self._ew(P, PR.SUBSAMPLE_GRAD, i=(N, cin, x.shape[2], x.shape[3], stride, 1), p=(dxs, tgt),
-                             nbytes=12.0 * tgt.numel())
+                if not (stage == 3 and j == 0):              # (the first trainable block sends nothing further down)
+                    # into the previous stage's output gradient, which already holds the lateral's part
+                    if c1_in is xs:
+                        dxs = self._pointwise_grad(P, l1, dz1, like=xs)
+                        dxs = self._pointwise_grad(P, lp, dz, into=dxs)
+                    else:
+                        # ResNeXt, stride 2: the two parts of the input gradient live at different sizes.  W1^T dz1 is
+                        # x-shaped: straight onto the previous stage's output gradient; Wp^T dz is xs-shaped: scattered
+                        # onto it afterwards.  Always in this order: same bits.  (In place, unlike _aux's rule for
+                        # gradients that meet: no auxiliary-stream launch reads that buffer -- the lateral's filter
+                        # gradient reads the stage output and dt -- and its first reader, the previous stage's
+                        # ReluGradient, is emitted on the main stream behind both writes.)
+                        grads_into[stage - 1] = self._pointwise_grad(P, l1, dz1, into=grads_into[stage - 1])
+                        dxs = self._pointwise_grad(P, lp, dz, like=xs)
+                    self._subsample_grad(P, dxs, grads_into[stage - 1], cin, stride, acc=True)
                 dy = None
                 dy_is_dz = False
             else:
                 # identity shortcut: dx = dz + W1^T dz1 (dz through the residual operand into a fresh
                 # buffer: the auxiliary stream may still be reading dz)
                 # x is the previous block's output y: its ReluGradient mask goes into this epilogue
-                dx = self._like(dz)
-                self._gemm(P, l1.w.view(cmid, cin), cin, dz1, dx, cmid, cin, res=dz, mask=x, fold=True)
-                dy = dx
+                dy = self._pointwise_grad(P, l1, dz1, like=dz, mask=x, res=dz, fold=True)
                 dy_is_dz = True
             if j == 0:
                 P.mark("bwd_res%d_done" % stage)
+
+    def _emit_p6p7_grad(self, P, c5, d6, d7, dc5):
+        """Backward of _emit_p6p7: both filter gradients, and c5's part of the data gradient written to dc5."""
+        D, S = self.D, self._fpn_saved
+        l6, l7 = self._layers["p6"], self._layers["p7"]
+        r6 = S["r6"]
+        # P7 = sub(conv(relu(p6)))
+        d7f = self._like(S["p7f"])
+        self._subsample_grad(P, d7, d7f, D, 2)
+        self._wgrad3(P, r6, d7f, l7)
+        dr6 = self._like(r6)
+        self._conv3(P, [(d7f, dr6, r6, l7.pd, None)], D, D, K.CONV_MASK_AUX, l7.engine)   # masked by p6 > 0
+        d6 = self._sum2(P, d6, dr6, D)
+        # P6 = sub(conv(c5))
+        d6f = self._like(S["p6f"])
+        self._subsample_grad(P, d6, d6f, D, 2)
+        self._wgrad3(P, c5, d6f, l6)
+        self._conv3(P, [(d6f, dc5, None, l6.pd, None)], l6.cin, D, 0, l6.engine)
+
+    def _emit_p6p7_own_grad(self, P, c5, d6, d7, dc5):
+        """Backward of _emit_p6p7_own."""
+        l6, l7 = self._layers["p6"], self._layers["p7"]
+        r6 = self._fpn_saved["r6"]
+        # P7 = conv_s2(relu(p6)): filter gradient, then the data gradient masked by p6 > 0, added to P6's own
+        self._wgrad_s2(P, r6, d7, l7)
+        dr6 = self._like(r6)
+        self._dgrad_s2(P, l7, d7, dr6, mask=r6)
+        d6 = self._sum2(P, d6, dr6, self.D)
+        # P6 = conv_s2(c5)
+        self._wgrad_s2(P, c5, d6, l6)
+        self._dgrad_s2(P, l6, d6, dc5)
 
     # -- running ---------------------------------------------------------------------------------------------
     def prepare(self):

@@ -10,11 +10,17 @@ leave the programs alone (a refactoring of the engine rules) must leave every ha
 
 It uses only Program.ops / .keep / .marks and the pipelines' constructors, so it runs against any commit:
 
-    python tests/golden/make_program_fingerprints.py --write       # tests/golden/program_fingerprints.json
+    python tests/golden/make_program_fingerprints.py --write       # tests/golden/program_fingerprints.json and
+                                                                   # backbone_buffers.json
     python tests/golden/make_program_fingerprints.py --dump NAME   # one configuration's readable listing
     python tests/golden/make_program_fingerprints.py --list
 
 A mismatch is located by diffing `--dump NAME` of the two commits.
+
+A record names a tensor that is not in Program.keep only by its order of appearance, so the listing does not pin the
+shape of an activation or gradient buffer.  backbone_buffers.json does: for every configuration that builds a backbone
+(an object with _bufs), the count of its buffers and a sha256 over the sorted list of their (dtype, shape).  Order of
+allocation is free.
 
 Canonical addresses: a ctypes table of Program.keep is T<ordinal of first appearance>(+offset); an address inside
 the storage of a tensor of Program.keep is S<ordinal of first appearance of that storage>+<byte offset>; any other
@@ -26,6 +32,7 @@ import argparse
 import bisect
 import contextlib
 import ctypes as C
+import functools
 import hashlib
 import json
 import os
@@ -37,6 +44,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 OUT = os.path.join(HERE, "program_fingerprints.json")
+OUT_BUFFERS = os.path.join(HERE, "backbone_buffers.json")
 
 SWITCHES = ("SSAD_SPLIT_CONV", "SSAD_STUDENT_F24", "SSAD_TEACHER_F24", "SSAD_CONV_ENGINE", "SSAD_STRIDED_3X3")
 SHAPES = [(10, 14), (5, 7)]
@@ -267,24 +275,59 @@ def configurations():
     out.append(("f16_x101_32x8d_wide_frozen", {},
                 backbone("x101-32x8d", cls=NativeResNetFPNF16, train=False, wide_groups=True)))
     out.append(("x101_64x4d_grouped_grad_train", {}, backbone("x101-64x4d", train=True, grouped_grad=True)))
+    # branches of the two backbone walks that the matrix above reaches at one width or in one precision only
+    wino = dict(SSAD_STRIDED_3X3="winograd")
+    out.append(("x101_32x8d_frozen", {}, backbone("x101-32x8d", train=False)))
+    out.append(("x101_32x8d_grouped_grad_train", {}, backbone("x101-32x8d", train=True, grouped_grad=True)))
+    out.append(("r101_train", {}, backbone("r101", train=True)))
+    out.append(("r50_strided_winograd_frozen", wino, backbone(train=False)))
+    out.append(("x101_64x4d_strided_winograd_grouped_grad_train", wino,
+                backbone("x101-64x4d", train=True, grouped_grad=True)))
+    out.append(("f16_r50_frozen", {}, backbone(cls=NativeResNetFPNF16, train=False)))
+    out.append(("f16_r101_train", {}, backbone("r101", cls=NativeResNetFPNF16, train=True)))
+    out.append(("f16_x101_64x4d_frozen", {}, backbone("x101-64x4d", cls=NativeResNetFPNF16, train=False)))
     return out
 
 
-def fingerprint(env, build):
-    """-> [sha256 of the listing, op count]"""
+def buffer_record(obj):
+    """[count, sha256 over the sorted (dtype, shape) list] of a backbone's activation / gradient / scratch buffers."""
+    shapes = sorted((str(t.dtype), tuple(t.shape)) for t in obj._bufs)
+    return [len(shapes), hashlib.sha256(repr(shapes).encode()).hexdigest()]
+
+
+def record(env, build):
+    """-> ([sha256 of the listing, op count], [buffer_record of every object that has _bufs])"""
     with _env(**env):
-        lines, nops = listing(build())
-    return [hashlib.sha256("\n".join(lines).encode()).hexdigest(), nops]
+        objects = build()
+        lines, nops = listing(objects)
+    return ([hashlib.sha256("\n".join(lines).encode()).hexdigest(), nops],
+            [buffer_record(o) for o in objects if hasattr(o, "_bufs")])
+
+
+@functools.lru_cache(maxsize=None)
+def records():
+    """Every configuration built once -> ({name: fingerprint}, {name: buffer records} of those that build a backbone)"""
+    fp, bufs = {}, {}
+    for name, env, build in configurations():
+        fp[name], b = record(env, build)
+        if b:
+            bufs[name] = b
+    return fp, bufs
 
 
 def fingerprints():
-    return {name: fingerprint(env, build) for name, env, build in configurations()}
+    return records()[0]
+
+
+def backbone_buffers():
+    return records()[1]
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--write", action="store_true", help="write %s" % os.path.relpath(OUT, ROOT))
     ap.add_argument("--out", default=OUT)
+    ap.add_argument("--out-buffers", default=OUT_BUFFERS)
     ap.add_argument("--dump", metavar="NAME", help="print one configuration's listing")
     ap.add_argument("--list", action="store_true", help="print the configurations' names")
     args = ap.parse_args()
@@ -298,13 +341,15 @@ def main():
                     print("\n".join(listing(build())[0]))
                 return
         raise SystemExit("no configuration %r (--list)" % args.dump)
-    fp = fingerprints()
+    fp, bufs = records()
     if args.write:
         commit = subprocess.check_output(["git", "rev-parse", "HEAD"], cwd=ROOT).decode().strip()
-        with open(args.out, "w") as f:
-            json.dump({"parent": commit, "configurations": fp}, f, indent=0, sort_keys=True)
-            f.write("\n")
-    print("%d configurations, %d distinct fingerprints" % (len(fp), len({v[0] for v in fp.values()})))
+        for path, conf in ((args.out, fp), (args.out_buffers, bufs)):
+            with open(path, "w") as f:
+                json.dump({"parent": commit, "configurations": conf}, f, indent=0, sort_keys=True)
+                f.write("\n")
+    print("%d configurations, %d distinct fingerprints, %d with backbone buffers" % (
+        len(fp), len({v[0] for v in fp.values()}), len(bufs)))
 
 
 if __name__ == "__main__":
